@@ -14,6 +14,15 @@ layers but serves N micro-batches per lane per step). Synthetic setup: random-in
 architecture generated directly on-device in the engine's q4_0 layout
 (identical compute + HBM traffic to a real checkpoint; no network for real
 weights — BASELINE.md).
+
+A plain run does only what the headline needs: set up, fill the KV, warm
+up, time `--steps` steps, print the JSON line. `--dump-outputs DIR` also
+writes what the last timed step computed (DIR/tokens.npy, hidden.npy,
+logits.npy, float32) so two builds can be compared output for output:
+weights and start tokens both derive from `--seed`, so equal arguments
+give equal inputs. `--full` is where measurements beyond the headline belong
+(none exist yet: every figure of the result line comes from the timed
+steps themselves).
 """
 from __future__ import annotations
 
@@ -39,6 +48,36 @@ FTYPES = {"q4_0": ggml.FTYPE_MOSTLY_Q4_0, "q4_1": ggml.FTYPE_MOSTLY_Q4_1,
           "q4_K": ggml.FTYPE_MOSTLY_Q4_K_M,
           "q5_K": ggml.FTYPE_MOSTLY_Q5_K_M, "q6_K": ggml.FTYPE_MOSTLY_Q6_K,
           "f16": ggml.FTYPE_MOSTLY_F16, "f32": ggml.FTYPE_ALL_F32}
+
+DUMP_BUDGET = 64 * 10**6  # bytes, all --dump-outputs files together
+
+
+def dump_outputs(pipe: DecodePipeline, out_dir: str) -> None:
+    """Write what the last timed step handed its caller, as float32 .npy:
+    rank 0 the sampled token ids [global_batch]; the last rank the final
+    hidden state [global_batch, E] and the logits [global_batch, V] those
+    ids were sampled from (rows in micro-batch order). An array over its
+    share of DUMP_BUDGET keeps a fixed, seeded sample of its rows."""
+    import numpy as np
+    arrays = {}
+    if pipe.is_first:
+        arrays["tokens"] = pipe.current_tokens().reshape(-1)
+    if pipe.is_last:
+        arrays["hidden"] = torch.cat([o[0] for o in pipe.last_out])
+        arrays["logits"] = torch.cat([o[1] for o in pipe.last_out])
+    os.makedirs(out_dir, exist_ok=True)
+    # the token ids (4 bytes per sequence) may live on another rank
+    budget = DUMP_BUDGET - 4 * pipe.cfg.global_batch
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if name != "tokens":
+            if a.nbytes > budget:
+                rows = max(1, budget // (a.nbytes // a.shape[0]))
+                keep = np.random.default_rng(0).choice(
+                    a.shape[0], size=rows, replace=False)
+                a = a[np.sort(keep)]
+            budget -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main() -> int:
@@ -76,7 +115,21 @@ def main() -> int:
                          "timing, so the headline is a steady-state "
                          "number over a ~this-deep KV, not a cold-cache "
                          "one (VERDICT r1). 0 = shallow/cold timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "outputs (token ids, final hidden state, "
+                         "logits) to DIR/<name>.npy as float32, at most "
+                         "64 MB in all; same arguments = same inputs, "
+                         "so two builds can be compared array by array")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that are not part "
+                         "of the headline figure (baselines, other "
+                         "precisions or sizes, reference comparisons). "
+                         "None exist yet, so this adds nothing to a "
+                         "plain run; new ones go behind this flag")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -85,6 +138,14 @@ def main() -> int:
 
     import torch.distributed as dist
     device = "cuda" if torch.cuda.is_available() else "cpu"
+    # --steps is never cut short (only the untimed prefill shrinks to
+    # fit, below), so a run that would step past the KV cache even with
+    # no prefill is refused before anything is allocated
+    cap_steps = 2 if device == "cuda" else 0  # capture_graphs' warmup
+    if cap_steps + args.warmup + args.steps > args.ctx:
+        ap.error(f"--warmup {args.warmup} + --steps {args.steps} (+ "
+                 f"{cap_steps} graph-capture steps) exceed --ctx "
+                 f"{args.ctx}")
     backend = ("nccl" if device == "cuda" else "gloo") \
         if args.backend == "auto" else args.backend
     if world > 1:
@@ -183,15 +244,19 @@ def main() -> int:
     # and so do capture_graphs' 2 eager warmup steps on the CUDA path
     # (at a clamped-to-ctx config, forgetting them writes the last KV
     # rows at pos >= n_ctx: out of bounds)
-    cap_steps = 2 if device == "cuda" else 0
     depth_end = cap_steps + args.prefill_depth + args.warmup + args.steps
     if depth_end > args.ctx:
         args.prefill_depth = max(0, args.ctx - args.warmup - args.steps
                                  - cap_steps)
         depth_end = (cap_steps + args.prefill_depth + args.warmup +
                      args.steps)
+    # the pipeline draws its start tokens from torch's global generator,
+    # which a fresh process seeds at random: pin it so equal arguments
+    # give equal inputs
+    torch.manual_seed(args.seed)
     pipe = DecodePipeline(eng, cfg, rank=rank, world=world,
                           engines=engines)
+    pipe.keep_outputs = args.dump_outputs is not None
     # the prefill steps run as extra (graph-replayed) warmup: real decode
     # work filling the KV with real activations — nothing in the timed
     # region is skipped or cached, it just starts at a stated depth
@@ -209,6 +274,9 @@ def main() -> int:
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+
+    if args.dump_outputs is not None:
+        dump_outputs(pipe, args.dump_outputs)
 
     tokens = args.steps * cfg.global_batch
     toks_per_s = tokens / elapsed

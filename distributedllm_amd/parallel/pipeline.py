@@ -123,6 +123,12 @@ class DecodePipeline:
         self._graph_out = None   # per-mb tensors the graph writes
         self._streams = None     # per-mb streams (single-GPU multi-mb)
         self.temperature = 0.0   # 0 = greedy argmax (graph-capturable)
+        # keep_outputs: the last stage keeps references to each micro-
+        # batch's latest (hidden, logits) in last_out[m] (under hipGraph
+        # replay these are the graph's static output tensors, refreshed
+        # by every replay). Set before capture_graphs; off = no refs held
+        self.keep_outputs = False
+        self.last_out = [None] * M
         # Host-staged hops: gloo cannot move CUDA tensors, but a gloo
         # pipeline with CUDA compute is how the multi-rank path is
         # shaken out on a 1-GPU box (RCCL refuses two ranks on one
@@ -207,6 +213,8 @@ class DecodePipeline:
                 nxt = torch.multinomial(probs, 1)[:, 0].to(torch.int32)
             else:
                 nxt = eng.argmax(lg)
+            if self.keep_outputs:
+                self.last_out[m] = (y, lg)
             if self.world == 1:
                 self.tok[m].copy_(nxt)
                 out = None

@@ -220,6 +220,61 @@ def test_bench_driver_contract():
             "parallelism"} <= set(r["config"])
 
 
+def _run_bench(*extra, timeout=150):
+    import subprocess
+    import sys
+    return subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "1", *extra],
+        capture_output=True, text=True, timeout=timeout,
+        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's outputs as
+    float32 .npy files; two runs with the same arguments (one of them
+    with `--full`, which adds nothing to the timed path) write identical
+    arrays, and the token ids are the argmax of the dumped logits. A
+    shallow KV keeps both runs short on any device."""
+    import numpy as np
+    small = ["--steps", "3", "--warmup", "1", "--ctx", "64",
+             "--prefill-depth", "4"]
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = _run_bench(*small, *extra, "--dump-outputs", str(d))
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        r = json.loads(lines[0])
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+        assert sorted(p.name for p in d.iterdir()) == \
+            ["hidden.npy", "logits.npy", "tokens.npy"]
+        arrs = {p.stem: np.load(p) for p in d.iterdir()}
+        B = r["config"]["global_batch"]
+        assert arrs["tokens"].shape == (B,)
+        assert arrs["hidden"].shape[0] == B and arrs["hidden"].ndim == 2
+        assert arrs["logits"].shape[0] == B and arrs["logits"].ndim == 2
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 10**6
+        for a in arrs.values():
+            assert a.dtype == np.float32 and np.isfinite(a).all()
+        assert np.array_equal(arrs["tokens"],
+                              arrs["logits"].argmax(axis=1))
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+def test_bench_refuses_steps_past_context():
+    """--steps is never cut short: a run whose warmup + timed steps
+    cannot fit the KV cache exits with an error instead of stepping
+    past it (or quietly timing fewer steps)."""
+    out = _run_bench("--steps", "40", "--warmup", "30", "--ctx", "64")
+    assert out.returncode != 0
+    assert "exceed --ctx" in out.stderr
+    assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
 def test_pipeline_generate_temperature_sampling():
     """temperature > 0 switches the last rank to softmax sampling:
     deterministic under a fixed torch seed, tokens within vocab, and a
@@ -323,16 +378,22 @@ def test_bench_driver_contract_world2():
     """The driver's N>1 launch shape (torch.distributed.run, one rank
     per GPU) must work end-to-end: rendezvous on 127.0.0.1, gloo on
     CPU, per-rank layer partition, MAX-over-ranks timing, ONE JSON line
-    from rank 0 with the world-2 aggregate."""
+    from rank 0 with the world-2 aggregate.
+
+    This is the CPU/gloo shape by design (it asserts the gloo backend),
+    so the ranks are started with the GPUs hidden: on a machine with a
+    single GPU both ranks would otherwise land on it with a full-size
+    KV set each and run out of memory."""
     import subprocess
     import sys
     port = str(29500 + os.getpid() % 500)
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", port, "bench.py", "--gpus", "2",
          "--steps", "2", "--warmup", "1"],
-        capture_output=True, text=True, timeout=300,
+        capture_output=True, text=True, timeout=300, env=env,
         cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
