@@ -423,6 +423,12 @@ class ServeHttpCommand(Command):
                             "shared decode step: up to K draft tokens "
                             "per greedy request verified per forward "
                             "(token-exact; 0 = off)")
+        p.add_argument("--device-sampling", action="store_true",
+                       help="sample temperature/penalty/top-k/top-p "
+                            "requests on the engine (one batched launch "
+                            "per lane and step) instead of copying the "
+                            "logits to the host; same tokens per seed up "
+                            "to f32 rounding at a CDF boundary")
         p.add_argument("--pipeline", action="store_true",
                        help="serve across torch.distributed pipeline "
                             "ranks (launch with torchrun, one rank per "
@@ -466,7 +472,8 @@ class ServeHttpCommand(Command):
         bat = ContinuousBatcher(eng, engines=lanes,
                                 prefill_chunk=args.prefill_chunk or None,
                                 spec_ngram=3 if args.speculate else 0,
-                                spec_k=args.speculate)
+                                spec_k=args.speculate,
+                                device_sampling=args.device_sampling)
         app, worker = build_http_app(bat, tok)
         try:
             uvicorn.run(app, host=args.host, port=args.port,
@@ -524,6 +531,11 @@ class ServeHttpCommand(Command):
             print("[serve] --speculate is single-engine only; "
                   "ignored under --pipeline", file=sys.stderr)
         spec = getattr(args, "speculate", 0) if world == 1 else 0
+        if getattr(args, "device_sampling", False):
+            # sampling happens on rank 0's host from the logits the last
+            # rank sends back; the facade has no sample()
+            print("[serve] --device-sampling is single-engine only; "
+                  "ignored under --pipeline", file=sys.stderr)
         bat = ContinuousBatcher(facade,
                                 prefill_chunk=args.prefill_chunk or None,
                                 spec_ngram=3 if spec else 0, spec_k=spec)

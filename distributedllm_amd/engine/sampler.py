@@ -70,3 +70,74 @@ class Sampler:
         tid = int(self.rng.choice(size, p=probs))
         self.previous_ids.append(tid)
         return tid
+
+    def draw_params(self):
+        """Next uniform of this request's RNG stream plus the filter
+        settings: (u, temperature, repeat_penalty, top_k, top_p). Drives
+        `sample_reference` / the engines' device `sample` from the same
+        object `__call__` serves; the caller appends the chosen id to
+        `previous_ids`."""
+        return (float(self.rng.random()), float(self.T),
+                float(self.penalty), int(self.top_k), float(self.top_p))
+
+
+def reference_probs(logits, prev_ids, temperature, repeat_penalty, top_k,
+                    top_p, dtype=np.float64):
+    """The distribution `sample_reference` draws from (steps 1-4 of its
+    docstring): filtered, renormalised probabilities over the vocabulary,
+    zero outside the kept set."""
+    logits = np.asarray(logits, dtype=dtype).reshape(-1)
+    size = logits.shape[0]
+    mask = np.zeros(size, dtype=bool)
+    if len(prev_ids):
+        mask[np.asarray(prev_ids, dtype=np.int64)] = True
+    penalties = ((mask * dtype(repeat_penalty) + ~mask) *
+                 (dtype(temperature) + dtype(Sampler.EPS)))
+    probs = softmax(logits / penalties)
+    if top_k and top_k < size:
+        kth = np.partition(probs, -top_k)[-top_k]
+        probs = np.where(probs >= kth, probs, 0.0)
+        probs = probs / probs.sum()
+    if top_p < 1.0:
+        order = np.argsort(-probs, kind="stable")
+        csum = np.cumsum(probs[order])
+        cut = min(int(np.searchsorted(csum, top_p)), size - 1)
+        tau = probs[order[cut]]
+        probs = np.where((probs >= tau) & (probs > 0), probs, 0.0)
+    if top_k or top_p < 1.0:
+        probs = probs / probs.sum()
+    return probs
+
+
+def sample_reference(logits, u, prev_ids, temperature, repeat_penalty,
+                     top_k, top_p, dtype=np.float64):
+    """Pure form of `Sampler.__call__` driven by one uniform `u` in
+    [0, 1): returns (token, kept_mask). These are the semantics the
+    device sampling kernel is checked against.
+
+    1. z_i = logit_i / (pen_i * (T + 1e-5)), pen_i = repeat_penalty for
+       ids in `prev_ids`, else 1 (negative logits are boosted, as in
+       `Sampler`).
+    2. p = softmax(z).
+    3. top_k (0 or >= V: off): keep p_i >= the k-th largest value, ties
+       at the threshold all kept; renormalise.
+    4. top_p (>= 1: off): tau = the largest value whose mass {p >= tau}
+       reaches top_p; keep p_i >= tau, ties all kept; renormalise. The
+       threshold form of "smallest sorted prefix" - equal to `Sampler`
+       whenever no tie sits on the boundary.
+    5. first index whose cumulative kept probability exceeds u - the
+       draw `Generator.choice(size, p=probs)` makes from
+       `Generator.random()`. A token outside the kept set is never
+       returned.
+    """
+    probs = reference_probs(logits, prev_ids, temperature, repeat_penalty,
+                            top_k, top_p, dtype)
+    size = probs.shape[0]
+    cdf = np.cumsum(probs)
+    cdf = cdf / cdf[-1]
+    tid = int(np.searchsorted(cdf, u, side="right"))
+    kept = probs > 0
+    if tid >= size or not kept[tid]:
+        # u within rounding of 1: the last kept token
+        tid = int(np.flatnonzero(kept)[-1])
+    return tid, kept

@@ -930,6 +930,57 @@ class HIPSliceEngine:
     def argmax(self, lg: torch.Tensor) -> torch.Tensor:
         return self._eng.argmax(lg)
 
+    # ---- on-device sampling (ops/csrc/sampling.hip) ----
+
+    def new_seen_state(self, n_slots: Optional[int] = None) -> torch.Tensor:
+        """Zeroed repetition bitmap [slots, ceil(V/32)]: bit i of slot s is
+        set once token i was sampled by the request in that slot."""
+        n = self.max_batch if n_slots is None else int(n_slots)
+        return torch.zeros(n, (self.hp.n_vocab + 31) // 32,
+                           dtype=torch.int32, device=self.device)
+
+    def reset_seen(self, seen: torch.Tensor, slot: int) -> None:
+        seen[slot].zero_()
+
+    def sample(self, lg: torch.Tensor, rows, slots, u, temperature,
+               repeat_penalty, top_k, top_p,
+               seen: torch.Tensor) -> torch.Tensor:
+        """Sample lg[rows[r]] for every r in ONE launch on the current
+        stream; per-row host sequences u (uniforms in [0, 1)),
+        temperature, repeat_penalty, top_k, top_p. Slots must be
+        distinct; seen[slots[r]] supplies the penalty set and gains the
+        chosen bit. One packed upload, returns device i32 ids [R] —
+        semantics of engine.sampler.sample_reference."""
+        R = len(rows)
+        rows = np.asarray(rows, dtype=np.int64)
+        slots = np.asarray(slots, dtype=np.int64)
+        if R == 0 or not (len(slots) == len(u) == len(temperature) ==
+                          len(repeat_penalty) == len(top_k) ==
+                          len(top_p) == R):
+            raise ValueError("sample: per-row arguments must share one "
+                             "non-zero length")
+        if rows.min() < 0 or rows.max() >= lg.shape[0]:
+            raise ValueError("sample: row index out of range")
+        if slots.min() < 0 or slots.max() >= seen.shape[0]:
+            raise ValueError("sample: slot index out of range")
+        if len(np.unique(slots)) != R:
+            raise ValueError("sample: slots must be distinct")
+        packed = np.empty((7, R), dtype=np.int32)
+        fl = packed.view(np.float32)
+        packed[0] = rows
+        packed[1] = slots
+        # the kernel's pick needs u < 1 after the f32 rounding
+        fl[2] = np.minimum(np.asarray(u, dtype=np.float64).astype(
+            np.float32), np.float32(1.0 - 2.0 ** -24))
+        fl[3] = np.asarray(temperature, dtype=np.float32)
+        fl[4] = np.asarray(repeat_penalty, dtype=np.float32)
+        packed[5] = np.clip(np.asarray(top_k, dtype=np.int64), 0,
+                            2 ** 31 - 1)
+        fl[6] = np.asarray(top_p, dtype=np.float32)
+        params = torch.from_numpy(packed).to(self.device)
+        return self._eng.sample(lg, params, seen, int(rows.max()),
+                                int(slots.max()))
+
 
 class TorchSliceEngine:
     """CPU twin with the identical stateless interface (fp32 torch math).
@@ -1018,6 +1069,35 @@ class TorchSliceEngine:
 
     def argmax(self, lg: torch.Tensor) -> torch.Tensor:
         return lg.argmax(dim=-1).to(torch.int32)
+
+    # ---- sampling twin: same interface as HIPSliceEngine, float64
+    # sample_reference per row, seen state as a plain bool tensor ----
+
+    def new_seen_state(self, n_slots: Optional[int] = None) -> torch.Tensor:
+        n = self.max_batch if n_slots is None else int(n_slots)
+        return torch.zeros(n, self.hp.n_vocab, dtype=torch.bool)
+
+    def reset_seen(self, seen: torch.Tensor, slot: int) -> None:
+        seen[slot].zero_()
+
+    def sample(self, lg: torch.Tensor, rows, slots, u, temperature,
+               repeat_penalty, top_k, top_p,
+               seen: torch.Tensor) -> torch.Tensor:
+        from .sampler import sample_reference
+        if len(set(int(s) for s in slots)) != len(rows):
+            raise ValueError("sample: slots must be distinct")
+        lg64 = lg.detach().to(torch.float64).numpy()
+        out = []
+        for r in range(len(rows)):
+            slot = int(slots[r])
+            prev = torch.nonzero(seen[slot]).reshape(-1).numpy()
+            tid, _ = sample_reference(
+                lg64[int(rows[r])], float(u[r]), prev,
+                float(temperature[r]), float(repeat_penalty[r]),
+                int(top_k[r]), float(top_p[r]))
+            seen[slot, tid] = True
+            out.append(tid)
+        return torch.tensor(out, dtype=torch.int32)
 
 
 def engine_for_slice(f: ggml.GGMLFile, n_ctx: int, max_batch: int,

@@ -17,7 +17,8 @@ CSRC = PKG_DIR / "csrc"
 SO_PATH = PKG_DIR / "_core.so"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
-SOURCES = [CSRC / "kernels.hip", CSRC / "engine_ext.cpp"]
+SOURCES = [CSRC / "kernels.hip", CSRC / "sampling.hip",
+           CSRC / "engine_ext.cpp"]
 HEADERS = [CSRC / "kernels.h"]
 
 

@@ -515,6 +515,45 @@ class SliceEngine {
         return out;
     }
 
+    // Batched sampling of R rows of lg in one launch (sampling.hip).
+    // params is one packed i32 [7, R] device tensor — rows, slots,
+    // u, temperature, penalty (f32 bits), top_k, top_p (f32 bits) — so a
+    // step costs one upload; seen is the [slots, ceil(V/32)] repetition
+    // bitmap (i32 storage), updated in place. row_max/slot_max are the
+    // host-side maxima of params[0]/params[1] (the values themselves live
+    // on the device; the kernel additionally refuses out-of-range ones).
+    torch::Tensor sample(torch::Tensor lg, torch::Tensor params,
+                         torch::Tensor seen, int64_t row_max,
+                         int64_t slot_max) {
+        check_f32(lg, "logits");
+        check_i32(params, "params");
+        check_i32(seen, "seen");
+        TORCH_CHECK(lg.dim() == 2, "sample: logits must be [T, V]");
+        const int T = (int)lg.size(0);
+        const int V = (int)lg.size(1);
+        TORCH_CHECK(params.dim() == 2 && params.size(0) == 7,
+                    "sample: params must be [7, R]");
+        const int R = (int)params.size(1);
+        TORCH_CHECK(R >= 1 && R <= maxP_, "sample: too many rows");
+        TORCH_CHECK(seen.dim() == 2 && seen.size(1) == (V + 31) / 32,
+                    "sample: seen must be [slots, ceil(V/32)]");
+        TORCH_CHECK(row_max >= 0 && row_max < T,
+                    "sample: row index out of range");
+        TORCH_CHECK(slot_max >= 0 && slot_max < seen.size(0),
+                    "sample: slot index out of range");
+        auto out = torch::empty(
+            {R},
+            torch::TensorOptions().device(torch::kCUDA).dtype(torch::kInt32));
+        hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+        const int* p = params.data_ptr<int>();
+        const float* pf = reinterpret_cast<const float*>(p);
+        launch_sample(s, lg.data_ptr<float>(), p, p + R, pf + 2 * R,
+                      pf + 3 * R, pf + 4 * R, p + 5 * R, pf + 6 * R,
+                      reinterpret_cast<uint32_t*>(seen.data_ptr<int>()),
+                      out.data_ptr<int>(), R, T, V, (int)seen.size(0));
+        return out;
+    }
+
     int64_t max_tokens() const { return kMaxTokens; }
     int64_t max_prefill() const { return maxP_; }
     int64_t n_ctx() const { return ctx_; }
@@ -590,6 +629,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("logits", &SliceEngine::logits, py::arg("x"),
              py::arg("all_logits") = false)
         .def("argmax", &SliceEngine::argmax)
+        .def("sample", &SliceEngine::sample, py::arg("logits"),
+             py::arg("params"), py::arg("seen"), py::arg("row_max"),
+             py::arg("slot_max"))
         .def_property_readonly("max_tokens", &SliceEngine::max_tokens)
         .def_property_readonly("max_prefill", &SliceEngine::max_prefill)
         .def_property_readonly("n_ctx", &SliceEngine::n_ctx)

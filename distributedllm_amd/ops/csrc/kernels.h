@@ -108,6 +108,16 @@ void launch_embed(hipStream_t s, const WMat& tab, const int* tokens,
 void launch_argmax(hipStream_t s, const float* logits,
                    unsigned long long* keys, int* out, int T, int V);
 
+// sampling.hip: one workgroup per entry of rows[R] samples logits[rows[r]]
+// with that entry's (u, temperature, penalty, top_k, top_p); reads and
+// updates the repetition bitmap seen[n_slots][ceil(V/32)] at slots[r]
+// (slots distinct within a launch). Out-of-range rows/slots yield id -1.
+void launch_sample(hipStream_t s, const float* logits, const int* rows,
+                   const int* slots, const float* u,
+                   const float* temperature, const float* penalty,
+                   const int* top_k, const float* top_p, uint32_t* seen,
+                   int* ids, int R, int T, int V, int n_slots);
+
 // ---------------------------------------------------------- prefill path
 // Large-M (T > 64) layer kernels: one launch covers all T tokens with an
 // XCD-aware (row-tile x 64-token-group) grid. Side channels use the

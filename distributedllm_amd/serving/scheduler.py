@@ -14,7 +14,9 @@ Semantics per request match the TCP client's `generate`
 prompt token at its true position and sample the continuation — greedy
 through the engine's device argmax, or per-request host `Sampler`
 (reference parity, including repetition penalty over that request's
-sampled ids only).
+sampled ids only). With `device_sampling=True` the sampled requests of
+a lane go through ONE `engine.sample` launch instead: the logits stay on
+the device and only the ids come back.
 """
 from __future__ import annotations
 
@@ -56,7 +58,8 @@ class ContinuousBatcher:
     def __init__(self, engine, max_slots: Optional[int] = None,
                  eos_id: Optional[int] = None, engines=None,
                  prefill_chunk: Optional[int] = None,
-                 spec_ngram: int = 0, spec_k: int = 0):
+                 spec_ngram: int = 0, spec_k: int = 0,
+                 device_sampling: bool = False):
         """engines: optional list of k weight-sharing clones ("lanes");
         global slot s lives on lane s%k as that clone's local slot s//k,
         and on CUDA each lane's forward runs on its own HIP stream —
@@ -79,7 +82,16 @@ class ContinuousBatcher:
         positions stay strictly sequential, so the same exactness
         guarantee holds per request). Sampled requests always advance
         one token. Token-exact with spec off — asserted in
-        tests/test_serving.py."""
+        tests/test_serving.py.
+
+        device_sampling: sample on the engine instead of the host. Each
+        request's `Sampler` still owns the RNG stream and the settings
+        (one uniform per step via `Sampler.draw_params`), but
+        `Sampler.__call__` never runs and the [rows, V] logits are never
+        copied to the host: a lane's sampled rows share one
+        `engine.sample` call on the lane's stream, with the repetition
+        state kept per lane-local slot on the device. Raises ValueError
+        if an engine has no `sample` (the pipeline facade)."""
         self.engine = engine
         self.lanes = engines if engines else [engine]
         k = len(self.lanes)
@@ -104,6 +116,14 @@ class ContinuousBatcher:
         self._streams = None
         if k > 1 and self._dev == "cuda":
             self._streams = [torch.cuda.Stream() for _ in self.lanes]
+        self.device_sampling = bool(device_sampling)
+        self._seen = None       # per-lane repetition state
+        if self.device_sampling:
+            if not all(hasattr(e, "sample") and
+                       hasattr(e, "new_seen_state") for e in self.lanes):
+                raise ValueError(
+                    "device_sampling needs an engine with sample()")
+            self._seen = [e.new_seen_state() for e in self.lanes]
 
     def _lane(self, slot: int):
         k = len(self.lanes)
@@ -205,6 +225,16 @@ class ContinuousBatcher:
         r._next_tok = r.prompt[-1]
         r._pos = len(r.prompt) - 1
         self.active[r.slot] = r
+        if self._seen is not None and r.sampler is not None:
+            # a reused slot must not inherit the previous request's
+            # repetition set; on the lane's stream so it orders with
+            # that lane's sample launches
+            k = len(self.lanes)
+            j = r.slot % k
+            ctx = (torch.cuda.stream(self._streams[j])
+                   if self._streams is not None else _nullctx())
+            with ctx:
+                self.lanes[j].reset_seen(self._seen[j], r.slot // k)
 
     # --------------------------------------------------------------- step
 
@@ -220,7 +250,7 @@ class ContinuousBatcher:
         per_lane: List[List[int]] = [[] for _ in range(k)]
         for s in sorted(self.active):
             per_lane[s % k].append(s)
-        work = []  # (reqs, drafts, greedy_ids, lg) per lane
+        work = []  # (reqs, drafts, greedy_ids, lg, sampled_ids) per lane
         for j, lane_slots in enumerate(per_lane):
             if not lane_slots:
                 continue
@@ -252,22 +282,55 @@ class ContinuousBatcher:
                 y = eng.forward(eng.embed(t), p, q, decode=decode)
                 lg = eng.logits(y, all_logits=True)
                 greedy_ids = None
-                if any(r.sampler is None for r in reqs):
+                if any(self._is_greedy(r) for r in reqs):
                     greedy_ids = eng.argmax(lg)
-            work.append((reqs, drafts, greedy_ids, lg))
+                sampled_ids = None
+                if self.device_sampling:
+                    sampled_ids = self._sample_lane(eng, j, lg, reqs,
+                                                    lane_slots, drafts)
+            work.append((reqs, drafts, greedy_ids, lg, sampled_ids))
         if self._streams is not None:
             for st in self._streams:
                 torch.cuda.current_stream().wait_stream(st)
 
         finished: List[Request] = []
-        for reqs, drafts, greedy_ids, lg in work:
+        for reqs, drafts, greedy_ids, lg, sampled_ids in work:
             if greedy_ids is not None and greedy_ids.device.type != "cpu":
                 greedy_ids = greedy_ids.cpu()
             lg_host = None
-            if any(r.sampler is not None for r in reqs):
+            if self.device_sampling:
+                if sampled_ids is not None:
+                    sampled_ids = sampled_ids.cpu().tolist()
+            elif any(r.sampler is not None for r in reqs):
                 lg_host = lg.float().cpu().numpy()
-            self._advance(reqs, drafts, greedy_ids, lg_host, finished)
+            self._advance(reqs, drafts, greedy_ids, lg_host, finished,
+                          sampled_ids)
         return finished
+
+    def _is_greedy(self, r: Request) -> bool:
+        """Served by the engine's argmax: no sampler, or (device
+        sampling) a sampler in greedy mode."""
+        return r.sampler is None or (self.device_sampling and
+                                     r.sampler.greedy)
+
+    def _sample_lane(self, eng, j, lg, reqs, lane_slots, drafts):
+        """One engine.sample call for the lane's sampled requests (in
+        request order, which _advance consumes); None if there are none.
+        Draws each request's next uniform."""
+        k = len(self.lanes)
+        rows, slots, params = [], [], []
+        row = 0
+        for r, s_, d in zip(reqs, lane_slots, drafts):
+            if not self._is_greedy(r):
+                rows.append(row)
+                slots.append(s_ // k)
+                params.append(r.sampler.draw_params())
+            row += 1 + len(d)
+        if not rows:
+            return None
+        u, temp, pen, top_k, top_p = zip(*params)
+        return eng.sample(lg, rows, slots, u, temp, pen, top_k, top_p,
+                          self._seen[j])
 
     def _draft(self, r: Request) -> List[int]:
         """Prompt-lookup draft for a greedy request (possibly empty)."""
@@ -282,11 +345,20 @@ class ContinuousBatcher:
         return lookup_draft(r.prompt + r.out, self.spec_ngram, k)
 
     def _advance(self, reqs, drafts, greedy_ids, lg_host,
-                 finished) -> None:
+                 finished, sampled_ids=None) -> None:
         row = 0
+        n_sampled = 0
         for r, draft in zip(reqs, drafts):
             nrows = 1 + len(draft)
-            if r.sampler is not None:
+            if self.device_sampling and r.sampler is not None:
+                if r.sampler.greedy:
+                    tid = int(greedy_ids[row])
+                else:
+                    tid = int(sampled_ids[n_sampled])
+                    n_sampled += 1
+                r.sampler.previous_ids.append(tid)
+                emit = [tid]
+            elif r.sampler is not None:
                 emit = [r.sampler(lg_host[row])]
             else:
                 nxt = [int(greedy_ids[row + i]) for i in range(nrows)]

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(
 import torch
 
 from distributedllm_amd.engine import HIPSliceEngine
+from distributedllm_amd.engine.sampler import Sampler
 from distributedllm_amd.formats import ggml
 from distributedllm_amd.models.llama import PRESETS
 from distributedllm_amd.serving import ContinuousBatcher
@@ -44,7 +45,21 @@ def main():
                          "random-init synthetic text repeats "
                          "unrealistically often — acceptance rates here "
                          "overstate real-text gains")
+    ap.add_argument("--temperature", type=float, default=None,
+                    help="sample every request at this temperature "
+                         "(default: greedy device argmax)")
+    ap.add_argument("--repeat-penalty", type=float, default=1.1)
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--seed", type=int, default=0,
+                    help="request i samples with seed + i")
+    ap.add_argument("--device-sampling", action="store_true",
+                    help="sample on the GPU (one batched launch per lane "
+                         "and step) instead of the per-request host "
+                         "Sampler over logits copied to the host")
     args = ap.parse_args()
+    if args.device_sampling and args.temperature is None:
+        ap.error("--device-sampling needs --temperature")
 
     hp = PRESETS[args.model].hparams(ggml.FTYPE_MOSTLY_Q4_0)
     eng = HIPSliceEngine.random(hp, n_layers=hp.n_layer, n_ctx=args.ctx,
@@ -57,10 +72,22 @@ def main():
     bat = ContinuousBatcher(eng, engines=lanes,
                             prefill_chunk=args.prefill_chunk or None,
                             spec_ngram=3 if args.speculate else 0,
-                            spec_k=args.speculate)
+                            spec_k=args.speculate,
+                            device_sampling=args.device_sampling)
+    n_sub = [0]
+
+    def sampler():
+        """Per-request sampler (None = greedy), seeded seed + i."""
+        if args.temperature is None:
+            return None
+        n_sub[0] += 1
+        return Sampler(args.temperature, args.repeat_penalty,
+                       seed=args.seed + n_sub[0] - 1, top_k=args.top_k,
+                       top_p=args.top_p)
+
     reqs = [bat.submit(torch.randint(3, hp.n_vocab, (args.prompt_len,),
                                      generator=g).tolist(),
-                       args.num_tokens)
+                       args.num_tokens, sampler=sampler())
             for _ in range(args.requests)]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -84,13 +111,19 @@ def main():
             for _ in range(args.long_requests):
                 reqs.append(bat.submit(
                     torch.randint(3, hp.n_vocab, (args.long_prompt,),
-                                  generator=g).tolist(), args.num_tokens))
+                                  generator=g).tolist(), args.num_tokens,
+                    sampler=sampler()))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     total = sum(len(r.out) for r in reqs)
     lat = sorted(done_at.values())
     p = lambda q: lat[min(len(lat) - 1, int(q * len(lat)))]
-    print(f"{args.requests} requests x {args.num_tokens} new tokens "
+    mode = "greedy" if args.temperature is None else (
+        f"sampled on {'device' if args.device_sampling else 'host'} "
+        f"T={args.temperature} rp={args.repeat_penalty} "
+        f"top_k={args.top_k} top_p={args.top_p}")
+    print(f"[{mode}] "
+          f"{args.requests} requests x {args.num_tokens} new tokens "
           f"(prompt {args.prompt_len}, {bat.n_slots} slots on "
           f"{len(bat.lanes)} lanes): "
           f"{total} tokens in {dt:.2f}s = {total/dt:.0f} tok/s, "
