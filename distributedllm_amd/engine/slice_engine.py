@@ -13,7 +13,7 @@ and recreates the llama_context) is here simply "start writing positions
 from 0 again" — cache slots are overwritten, nothing to reset.
 
 The HIP engine repacks on-disk q4 AoS blocks into the SoA layout the
-kernels stream (scales ‖ nibbles, see csrc/kernels.hip); repacking happens
+kernels stream (scales ‖ nibbles, see csrc/mfma_gemm.hip); repacking happens
 once at load on the host, uploads via torch pinned copies.
 """
 from __future__ import annotations
@@ -487,7 +487,7 @@ def repack_mfma(t: ggml.GGMLTensor, device: str):
         # per-(row, block) (alpha, beta) f16 pair; the kernel computes
         # w = alpha*((1024+n) + csub) + beta with csub = -1032 (q4_0,
         # giving alpha*(n-8)) or -1024 (q4_1, giving alpha*n + beta) in
-        # exact packed-f16 arithmetic (kernels.hip a_frag_q4); pad blocks
+        # exact packed-f16 arithmetic (mfma_gemm.hip a_frag_q4); pad blocks
         # carry alpha=beta=0 and contribute exact zeros.
         bs = 18 if t.gtype == ggml.GGML_TYPE_Q4_0 else 20
         a = np.frombuffer(t.raw, np.uint8).reshape(rows, nb, bs)

@@ -17,9 +17,10 @@ CSRC = PKG_DIR / "csrc"
 SO_PATH = PKG_DIR / "_core.so"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
-SOURCES = [CSRC / "kernels.hip", CSRC / "sampling.hip",
+SOURCES = [CSRC / "mfma_gemm.hip", CSRC / "attention.hip",
+           CSRC / "scalar_ops.hip", CSRC / "sampling.hip",
            CSRC / "engine_ext.cpp"]
-HEADERS = [CSRC / "kernels.h"]
+HEADERS = [CSRC / "kernels.h", CSRC / "device_common.h"]
 
 
 def _torch_paths():

@@ -4,7 +4,7 @@
 // (/root/reference/distllm/tensor_processor.cpp:2238-2260 exposed 9 functions
 // around a global TransformerSlice). This engine instead:
 //   * is an explicit object (no global mutable slice, SURVEY.md §5.2 hazard),
-//   * keeps weights resident in HBM3E in MFMA-tiled layouts (kernels.hip),
+//   * keeps weights resident in HBM3E in MFMA-tiled layouts (mfma_gemm.hip),
 //   * exchanges activations as torch tensors (DLPack-compatible device
 //     buffers), never per-element Python lists,
 //   * is stateless w.r.t. generation: positions/sequence ids are explicit
@@ -34,7 +34,7 @@ namespace {
 constexpr int kMaxTokens = 64;  // per-forward token cap (4 MFMA col tiles)
 
 // Tail slack appended to every MFMA-path allocation: the pipelined K loop
-// prefetches ONE load batch past its range (kernels.hip wave_tile_kloop).
+// prefetches ONE load batch past its range (mfma_gemm.hip wave_tile_kloop).
 constexpr int64_t kTailSlackQ = 256;     // int32 elements (1 KiB)
 constexpr int64_t kTailSlackQ8 = 512;    // int32 elements (byte stream)
 constexpr int64_t kTailSlackAB = 128;    // f16 elements (256 B)
@@ -435,11 +435,10 @@ class SliceEngine {
                 launch_gemm16(s, l.mo.w, aprep, nullptr, nullptr, eps_, xp,
                               xprep, ssf + li * ssw_, T, GM_RES_SQ);
             }
-            // ffn keeps the fused RT=1 kernel: the slab+finish variant
-            // measured slower at every split/occupancy combination tried
+            // ffn stays fused: a slab+finish variant measured slower at
+            // every split/occupancy combination tried and was removed
             launch_ffn16(s, l.m1.w, l.m3.w, xprep, u16p(l.ffn_normprep),
-                         ssf + li * ssw_, eps_, gprep, T,
-                         /*slab=*/nullptr);
+                         ssf + li * ssw_, eps_, gprep, T);
             if (split) {
                 launch_gemm16(s, l.m2.w, gprep, nullptr, nullptr, eps_,
                               slab, nullptr, nullptr, T, GM_SLAB);

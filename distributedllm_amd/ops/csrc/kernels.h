@@ -1,4 +1,6 @@
-// Launch API of the CDNA4 kernel library (kernels.hip).
+// Launch API of the CDNA4 kernel library: mfma_gemm.hip (MFMA dequant-GEMM
+// family), attention.hip, scalar_ops.hip (embed, argmax, legacy f32 path)
+// and sampling.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,7 +16,9 @@
 enum WType { W_F32 = 0, W_F16 = 1, W_Q4_0 = 2, W_Q4_1 = 3, W_Q8B = 8,
              W_Q8B16 = 9 };
 
-// One weight matrix resident in HBM, repacked SoA (see kernels.hip header).
+// One row-major weight matrix resident in HBM, SoA (scalar_ops.hip): the
+// embedding table in any of its four types, and the f32 matrices of the
+// legacy layer path (the GEMV kernels read `data` as f32 only).
 struct WMat {
     const void* data;    // f16/f32 values, or u8 nibbles for q4_*
     const void* scales;  // q4_0: f16[rows][nb]; q4_1: f16[rows][nb*2] (d,m)
@@ -23,11 +27,8 @@ struct WMat {
     int wtype;  // WType
 };
 
-// MFMA-tiled weight matrix (the production decode path). Layouts, with
-// R = rows/16 row-tiles and nb = cols/32 q4 blocks:
-//   q4_0/q4_1: data   = u32[R][nb][4][16]   (nibble words, see kernels.hip)
-//              scales = f32[R][nb][16]      (q4_1: float2 (d, m))
-//   W_F16    : data   = bf16[R][cols/8][16][8]  (weights converted to bf16)
+// MFMA-tiled weight matrix (the production path); the layouts are given
+// in the mfma_gemm.hip header.
 struct WMat2 {
     const void* data;
     const void* scales;
@@ -36,12 +37,13 @@ struct WMat2 {
     int wtype;  // WType (W_F32 never appears here — legacy path)
 };
 
-// k_gemm16 fused-epilogue modes. GM_ATOMIC = grid-level split-K partials
-// atomicAdd'ed into y (residual pre-loaded); follow with launch_prep_x.
-enum GemmMode { GM_PLAIN = 0, GM_RES_SQ = 1, GM_NORM_PLAIN = 2,
-                GM_ATOMIC = 3, GM_SLAB = 4 };
+// k_gemm16 modes: fused residual + sumsq + xprep epilogue; input RMSNorm +
+// plain store (lm_head); split-K partials into slabs (follow with
+// launch_reduce_prep). The values are template arguments of the kernels —
+// keep them stable. (0 and 3 were a plain store and an atomic split-K.)
+enum GemmMode { GM_RES_SQ = 1, GM_NORM_PLAIN = 2, GM_SLAB = 4 };
 
-// split-K factor used by GM_ATOMIC/GM_SLAB (shared with the reducer)
+// split-K factor used by GM_SLAB (shared with the reducer)
 int gemm16_ks(int rows);
 
 // y[t] += sum of ks slab partials, then sumsq + f16 xprep of the result
@@ -74,7 +76,7 @@ int qkv16_ks(int E, int Ekv);
 void launch_ffn16(hipStream_t s, const WMat2& w1, const WMat2& w3,
                   const unsigned short* xprep,
                   const unsigned short* normprep, const float* ss_in,
-                  float eps, unsigned short* gprep, int T, float* slab);
+                  float eps, unsigned short* gprep, int T);
 
 void launch_rmsnorm(hipStream_t s, const float* x, const float* w, float* y,
                     int T, int E, float eps);
@@ -124,8 +126,9 @@ void launch_sample(hipStream_t s, const float* logits, const int* rows,
 // jt_width(T) token-panel stride.
 int jt_width(int T);
 
-// Q-tiled (16 queries/block) streaming attention for prefill: each K/V
-// row is read once per 16 queries; mixed-seq tiles segment internally
+// Q-tiled (16 queries/block) matrix-core flash attention for prefill: each
+// K/V row is read once per 16 queries; mixed-seq tiles segment internally.
+// Requires D <= 128 (checked by the SliceEngine constructor).
 void launch_attn_prefill(hipStream_t s, const float* q_buf,
                          const __half* k_cache_layer,
                          const __half* v_cache_layer, float* out,
