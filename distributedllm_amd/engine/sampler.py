@@ -11,6 +11,9 @@
 A greedy mode mirrors the engine's device argmax semantics. Optional
 ``top_k``/``top_p`` (nucleus) filtering extends the reference surface
 (off by default — defaults are exact reference behavior).
+
+`logprobs_reference` is the float64 definition of the per-token
+log-probabilities the serving surfaces report.
 """
 from __future__ import annotations
 
@@ -141,3 +144,36 @@ def sample_reference(logits, u, prev_ids, temperature, repeat_penalty,
         # u within rounding of 1: the last kept token
         tid = int(np.flatnonzero(kept)[-1])
     return tid, kept
+
+
+LOGPROBS_MAX_TOP = 8   # kernels.h; the serving surfaces accept 0..8
+
+
+def logprobs_reference(logits_row, token_id, top_n=0):
+    """Log-probability of `token_id` under softmax of the RAW logits row
+    (full vocabulary, float64): (lp, top_ids[top_n], top_lp[top_n]).
+
+    Temperature, repetition penalty, top-k and top-p do not enter - the
+    OpenAI convention: log-probabilities describe the model, not the
+    sampler. `top_ids` are the `top_n` largest logits in descending
+    order, a tie resolving to the smaller index (the device argmax rule);
+    `top_lp` their log-probabilities. A -inf logit has log-probability
+    -inf. These are the semantics the device logprobs kernel is checked
+    against."""
+    x = np.asarray(logits_row, dtype=np.float64).reshape(-1)
+    size = x.shape[0]
+    top_n = int(top_n)
+    if top_n < 0 or top_n > size:
+        raise ValueError(f"top_n={top_n} outside 0..V={size}")
+    token_id = int(token_id)
+    if not 0 <= token_id < size:
+        raise ValueError(f"token id {token_id} outside the vocabulary")
+    m = x.max()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lse = m + np.log(np.exp(x - m).sum())
+        # stable sort of the negated row: descending, equal values in
+        # index order
+        top_ids = np.argsort(-x, kind="stable")[:top_n].astype(np.int64)
+        top_lp = x[top_ids] - lse
+        lp = float(x[token_id] - lse)
+    return lp, top_ids, top_lp

@@ -26,6 +26,7 @@ import torch
 
 from ..formats import ggml, q4
 from ..models.llama import RMS_EPS, ROPE_BASE, rms_norm, rope_interleaved
+from .sampler import LOGPROBS_MAX_TOP
 
 
 def _nibbles(t: ggml.GGMLTensor) -> np.ndarray:
@@ -981,6 +982,35 @@ class HIPSliceEngine:
         return self._eng.sample(lg, params, seen, int(rows.max()),
                                 int(slots.max()))
 
+    # ---- per-token log-probabilities (ops/csrc/logprobs.hip) ----
+
+    def logprobs(self, lg: torch.Tensor, rows, ids: torch.Tensor,
+                 top_n: int = 0):
+        """Raw log-softmax value of token ids[r] in lg[rows[r]] plus the
+        top_n most likely tokens of that row, for every r in ONE launch
+        on the current stream. `rows` is a host sequence (one packed
+        upload); `ids` a device i32 tensor [R] - the output of `argmax`
+        or `sample` goes in without leaving the GPU. Returns device
+        tensors (lp [R] f32, top_ids [R, top_n] i32, top_lp [R, top_n]
+        f32) - semantics of engine.sampler.logprobs_reference. An id
+        outside the vocabulary yields lp = NaN."""
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        R = len(rows)
+        top_n = int(top_n)
+        if R == 0 or ids.dim() != 1 or ids.shape[0] != R:
+            raise ValueError("logprobs: rows and ids must share one "
+                             "non-zero length")
+        if rows.min() < 0 or rows.max() >= lg.shape[0]:
+            raise ValueError("logprobs: row index out of range")
+        if not 0 <= top_n <= LOGPROBS_MAX_TOP:
+            raise ValueError(
+                f"logprobs: top_n must be in 0..{LOGPROBS_MAX_TOP}")
+        if top_n > lg.shape[1]:
+            raise ValueError("logprobs: top_n exceeds the vocabulary")
+        rows_dev = torch.from_numpy(rows.astype(np.int32)).to(self.device)
+        return self._eng.logprobs(lg, rows_dev, ids, top_n,
+                                  int(rows.max()))
+
 
 class TorchSliceEngine:
     """CPU twin with the identical stateless interface (fp32 torch math).
@@ -1098,6 +1128,33 @@ class TorchSliceEngine:
             seen[slot, tid] = True
             out.append(tid)
         return torch.tensor(out, dtype=torch.int32)
+
+    def logprobs(self, lg: torch.Tensor, rows, ids: torch.Tensor,
+                 top_n: int = 0):
+        """Twin of HIPSliceEngine.logprobs: float64 logprobs_reference
+        per row, rounded to the f32 / i32 result tensors."""
+        from .sampler import logprobs_reference
+        R = len(rows)
+        top_n = int(top_n)
+        if R == 0 or ids.dim() != 1 or ids.shape[0] != R:
+            raise ValueError("logprobs: rows and ids must share one "
+                             "non-zero length")
+        if min(rows) < 0 or max(rows) >= lg.shape[0]:
+            raise ValueError("logprobs: row index out of range")
+        if not 0 <= top_n <= LOGPROBS_MAX_TOP:
+            raise ValueError(
+                f"logprobs: top_n must be in 0..{LOGPROBS_MAX_TOP}")
+        if top_n > lg.shape[1]:
+            raise ValueError("logprobs: top_n exceeds the vocabulary")
+        lg64 = lg.detach().to(torch.float64).numpy()
+        lp = np.empty(R, dtype=np.float32)
+        top_ids = np.empty((R, top_n), dtype=np.int32)
+        top_lp = np.empty((R, top_n), dtype=np.float32)
+        for r in range(R):
+            lp[r], top_ids[r], top_lp[r] = logprobs_reference(
+                lg64[int(rows[r])], int(ids[r]), top_n)
+        return (torch.from_numpy(lp), torch.from_numpy(top_ids),
+                torch.from_numpy(top_lp))
 
 
 def engine_for_slice(f: ggml.GGMLFile, n_ctx: int, max_batch: int,

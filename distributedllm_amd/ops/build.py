@@ -19,7 +19,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 SOURCES = [CSRC / "mfma_gemm.hip", CSRC / "attention.hip",
            CSRC / "scalar_ops.hip", CSRC / "sampling.hip",
-           CSRC / "engine_ext.cpp"]
+           CSRC / "logprobs.hip", CSRC / "engine_ext.cpp"]
 HEADERS = [CSRC / "kernels.h", CSRC / "device_common.h"]
 
 

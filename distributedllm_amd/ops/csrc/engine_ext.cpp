@@ -553,6 +553,41 @@ class SliceEngine {
         return out;
     }
 
+    // Log-probabilities of R chosen tokens in one launch (logprobs.hip).
+    // rows is a device i32 [R] tensor uploaded by the caller (row_max is
+    // its host-side maximum), ids a device i32 [R] tensor that may come
+    // straight from argmax/sample. Returns (lp [R] f32, top_ids
+    // [R, top_n] i32, top_lp [R, top_n] f32).
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> logprobs(
+        torch::Tensor lg, torch::Tensor rows, torch::Tensor ids,
+        int64_t top_n, int64_t row_max) {
+        check_f32(lg, "logits");
+        check_i32(rows, "rows");
+        check_i32(ids, "ids");
+        TORCH_CHECK(lg.dim() == 2, "logprobs: logits must be [T, V]");
+        const int T = (int)lg.size(0);
+        const int V = (int)lg.size(1);
+        TORCH_CHECK(rows.dim() == 1 && ids.dim() == 1 &&
+                        rows.size(0) == ids.size(0) && rows.size(0) >= 1,
+                    "logprobs: rows and ids must be [R], R >= 1");
+        const int R = (int)rows.size(0);
+        TORCH_CHECK(top_n >= 0 && top_n <= LOGPROBS_MAX_TOP && top_n <= V,
+                    "logprobs: top_n out of range");
+        TORCH_CHECK(row_max >= 0 && row_max < T,
+                    "logprobs: row index out of range");
+        auto f32 = torch::TensorOptions().device(torch::kCUDA).dtype(
+            torch::kFloat32);
+        auto lp = torch::empty({R}, f32);
+        auto top_lp = torch::empty({R, top_n}, f32);
+        auto top_ids = torch::empty({R, top_n}, f32.dtype(torch::kInt32));
+        hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+        launch_logprobs(s, lg.data_ptr<float>(), rows.data_ptr<int>(),
+                        ids.data_ptr<int>(), lp.data_ptr<float>(),
+                        top_ids.data_ptr<int>(), top_lp.data_ptr<float>(), R,
+                        T, V, (int)top_n);
+        return {lp, top_ids, top_lp};
+    }
+
     int64_t max_tokens() const { return kMaxTokens; }
     int64_t max_prefill() const { return maxP_; }
     int64_t n_ctx() const { return ctx_; }
@@ -631,6 +666,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("sample", &SliceEngine::sample, py::arg("logits"),
              py::arg("params"), py::arg("seen"), py::arg("row_max"),
              py::arg("slot_max"))
+        .def("logprobs", &SliceEngine::logprobs, py::arg("logits"),
+             py::arg("rows"), py::arg("ids"), py::arg("top_n"),
+             py::arg("row_max"))
         .def_property_readonly("max_tokens", &SliceEngine::max_tokens)
         .def_property_readonly("max_prefill", &SliceEngine::max_prefill)
         .def_property_readonly("n_ctx", &SliceEngine::n_ctx)

@@ -1,6 +1,6 @@
 // Launch API of the CDNA4 kernel library: mfma_gemm.hip (MFMA dequant-GEMM
-// family), attention.hip, scalar_ops.hip (embed, argmax, legacy f32 path)
-// and sampling.hip.
+// family), attention.hip, scalar_ops.hip (embed, argmax, legacy f32 path),
+// sampling.hip and logprobs.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -119,6 +119,16 @@ void launch_sample(hipStream_t s, const float* logits, const int* rows,
                    const float* temperature, const float* penalty,
                    const int* top_k, const float* top_p, uint32_t* seen,
                    int* ids, int R, int T, int V, int n_slots);
+
+// logprobs.hip: one workgroup per entry of rows[R] writes the raw
+// log-softmax value of token ids[r] in logits[rows[r]] to lp[r], and the
+// top_n largest logits of that row (descending, ties to the smaller
+// index) as top_ids[r][top_n] / top_lp[r][top_n]. ids is a device array.
+// An out-of-range rows[r] or ids[r] yields lp[r] = NaN and no other write.
+constexpr int LOGPROBS_MAX_TOP = 8;
+void launch_logprobs(hipStream_t s, const float* logits, const int* rows,
+                     const int* ids, float* lp, int* top_ids, float* top_lp,
+                     int R, int T, int V, int top_n);
 
 // ---------------------------------------------------------- prefill path
 // Large-M (T > 64) layer kernels: one launch covers all T tokens with an

@@ -15,13 +15,22 @@ Endpoints:
              "temperature": float = 0.0 (0 = greedy),
              "repeat_penalty": float = 1.1, "seed": int | None,
              "top_k": int = 0, "top_p": float = 1.0,
-             "stop": [str, ...] | None}  # end at first stop string
-  POST /generate_stream   -> SSE, one data: line per token piece
-  POST /v1/completions    -> OpenAI-compatible completions shape
+             "stop": [str, ...] | None,  # end at first stop string
+             "logprobs": int | None}     # 0..8: per-token logprobs
+      with "logprobs" set the response gains
+      "logprobs": {"token_logprobs": [...], "top_logprobs": [[{"id",
+      "token", "logprob"}, ...], ...]} (raw-logit log-softmax, independent
+      of the sampler settings; -inf serialises as null)
+  POST /generate_stream   -> SSE, one data: line per token piece (plus
+      "logprob" / "top_logprobs" per event when "logprobs" is set)
+  POST /v1/completions    -> OpenAI-compatible completions shape; integer
+      "logprobs" fills choices[0].logprobs (tokens, token_logprobs,
+      top_logprobs, text_offset)
   GET  /metrics           -> lifetime counters incl. tokens_per_step
 """
 from __future__ import annotations
 
+import math
 import threading
 import time
 from typing import Optional
@@ -42,6 +51,19 @@ class GenerateRequest(BaseModel):
     stop: Optional[list] = None    # stop strings: generation ends when
     #                                the decoded continuation contains
     #                                one; the stop text is not returned
+    logprobs: Optional[int] = None  # 0..8: the chosen token's logprob plus
+    #                                that many most likely alternatives
+
+
+def _json_lp(v):
+    """JSON has no -inf/NaN: a zero-probability token reports null."""
+    v = float(v)
+    return v if math.isfinite(v) else None
+
+
+def _top_entries(tokenizer, top):
+    return [{"id": t, "token": tokenizer.decode_token(t),
+             "logprob": _json_lp(p)} for t, p in top]
 
 
 def trim_at_stop(tokenizer, ids, stops):
@@ -109,12 +131,13 @@ class BatcherWorker:
     def submit_and_wait(self, prompt_ids, max_new,
                         sampler: Optional[Sampler],
                         timeout: float = 300.0,
-                        stop_check=None):
+                        stop_check=None, logprobs: Optional[int] = None):
         """stop_check(req) -> bool: called on every step wake; True
         cancels the request (used for stop-string termination — the
         caller trims the output afterwards)."""
         with self.cond:
-            req = self.batcher.submit(prompt_ids, max_new, sampler=sampler)
+            req = self.batcher.submit(prompt_ids, max_new, sampler=sampler,
+                                      logprobs=logprobs)
             self.cond.notify_all()
             deadline = time.monotonic() + timeout
             seen = 0
@@ -181,8 +204,10 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
                 return any(s in tokenizer.decode(req.out) for s in stops)
         try:
             req = worker.submit_and_wait(ids, r.num_tokens, sampler,
-                                         stop_check=check)
-        except ValueError as e:        # oversized prompt+num_tokens
+                                         stop_check=check,
+                                         logprobs=r.logprobs)
+        except ValueError as e:        # oversized prompt+num_tokens, or
+            #                            logprobs the batcher rejects
             raise HTTPException(422, str(e))
         except TimeoutError as e:
             raise HTTPException(504, str(e))
@@ -191,7 +216,16 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
             toks, text, _ = trim_at_stop(tokenizer, req.out, stops)
         stats["requests"] += 1
         stats["tokens"] += len(toks)
-        return {"text": text, "tokens": toks}
+        out = {"text": text, "tokens": toks}
+        if r.logprobs is not None:
+            # trimmed with the tokens when a stop string cut the output
+            n = len(toks)
+            out["logprobs"] = {
+                "token_logprobs": [_json_lp(v)
+                                   for v in req.out_logprobs[:n]],
+                "top_logprobs": [_top_entries(tokenizer, top)
+                                 for top in req.out_top[:n]]}
+        return out
 
     @app.post("/generate_stream")
     def generate_stream(r: GenerateRequest):
@@ -207,10 +241,20 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
         stops = [s for s in (r.stop or []) if s]
         with worker.cond:
             try:
-                req = batcher.submit(ids, r.num_tokens, sampler=sampler)
+                req = batcher.submit(ids, r.num_tokens, sampler=sampler,
+                                     logprobs=r.logprobs)
             except ValueError as e:
                 raise HTTPException(422, str(e))
             worker.cond.notify_all()
+
+        def event(tid, piece, i):
+            d = {"token": tid, "piece": piece}
+            if r.logprobs is not None:
+                d["logprob"] = _json_lp(req.out_logprobs[i])
+                if r.logprobs > 0:
+                    d["top_logprobs"] = _top_entries(tokenizer,
+                                                     req.out_top[i])
+            return "data: " + _json.dumps(d) + "\n\n"
 
         def events():
             sent = 0
@@ -221,9 +265,10 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
                         while len(req.out) == sent and not req.done:
                             worker.cond.wait(timeout=1.0)
                         chunk = list(req.out[sent:])
+                        base = sent
                         sent = len(req.out)
                         done = req.done
-                    for tid in chunk:
+                    for i, tid in enumerate(chunk, base):
                         piece = tokenizer.decode_token(tid)
                         if stops:
                             cand = text + piece
@@ -238,9 +283,7 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
                                 # trimmed text)
                                 tail = cand[len(text):cut]
                                 if tail:
-                                    yield ("data: " + _json.dumps(
-                                        {"token": tid, "piece": tail})
-                                        + "\n\n")
+                                    yield event(tid, tail, i)
                                 with worker.cond:
                                     batcher.cancel(req)
                                 yield ("event: done\ndata: " +
@@ -249,8 +292,7 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
                                        + "\n\n")
                                 return
                             text = cand
-                        yield ("data: " + _json.dumps(
-                            {"token": tid, "piece": piece}) + "\n\n")
+                        yield event(tid, piece, i)
                     if done:
                         yield ("event: done\ndata: " + _json.dumps(
                             {"text": tokenizer.decode(req.out),
@@ -289,7 +331,28 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
             top_p=float(body.get("top_p", 1.0)),
             seed=body.get("seed"),
             stop=stop)
+        want_lp = body.get("logprobs")
+        if want_lp is not None:
+            if isinstance(want_lp, bool) or not isinstance(want_lp, int):
+                raise HTTPException(400, "logprobs must be an integer")
+            r.logprobs = want_lp
         out = generate(r)
+        lp = None
+        if want_lp is not None:
+            # OpenAI shape; text_offset indexes the returned text
+            pieces = [tokenizer.decode_token(t) for t in out["tokens"]]
+            offs, at = [], 0
+            for t in out["tokens"]:     # decode() drops BOS/EOS pieces
+                offs.append(min(at, len(out["text"])))
+                at += len(tokenizer.decode([t]))
+            lp = {"tokens": pieces,
+                  "token_logprobs": out["logprobs"]["token_logprobs"],
+                  # ids that decode to one piece share a key: the most
+                  # likely one keeps it
+                  "top_logprobs": [{e["token"]: e["logprob"]
+                                    for e in reversed(top)} for top in
+                                   out["logprobs"]["top_logprobs"]],
+                  "text_offset": offs}
         stats["v1_id"] = stats.get("v1_id", 0) + 1
         return {
             "id": f"cmpl-{stats['v1_id']}",
@@ -298,7 +361,7 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
             "choices": [{
                 "text": out["text"],
                 "index": 0,
-                "logprobs": None,
+                "logprobs": lp,
                 "finish_reason":
                     "length" if len(out["tokens"]) >= r.num_tokens
                     else "stop",

@@ -16,18 +16,21 @@ through the engine's device argmax, or per-request host `Sampler`
 (reference parity, including repetition penalty over that request's
 sampled ids only). With `device_sampling=True` the sampled requests of
 a lane go through ONE `engine.sample` launch instead: the logits stay on
-the device and only the ids come back.
+the device and only the ids come back. A request submitted with
+`logprobs=n` also records each emitted token's log-probability and the n
+most likely alternatives: one `engine.logprobs` launch per lane over the
+device ids of argmax / sample, results in the same host sync as the ids.
 """
 from __future__ import annotations
 
 from collections import deque
 from contextlib import nullcontext as _nullctx
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from ..engine.sampler import Sampler
+from ..engine.sampler import LOGPROBS_MAX_TOP, Sampler, logprobs_reference
 from .speculative import lookup_draft
 
 
@@ -44,6 +47,11 @@ class Request:
     _next_tok: int = -1   # token to feed at _pos on the next step
     _pos: int = -1
     _pf_pos: int = 0      # prompt tokens already prefilled (chunked)
+    # None = off; n >= 0: the chosen token's log-probability plus the n
+    # most likely tokens, per generated token (index-aligned with `out`)
+    logprobs: Optional[int] = None
+    out_logprobs: List[float] = field(default_factory=list)
+    out_top: List[List[Tuple[int, float]]] = field(default_factory=list)
 
 
 class ContinuousBatcher:
@@ -118,6 +126,9 @@ class ContinuousBatcher:
             self._streams = [torch.cuda.Stream() for _ in self.lanes]
         self.device_sampling = bool(device_sampling)
         self._seen = None       # per-lane repetition state
+        # set by the first submit(logprobs=...): until then a step does
+        # not even look at the requests' logprobs fields
+        self._logprobs_seen = False
         if self.device_sampling:
             if not all(hasattr(e, "sample") and
                        hasattr(e, "new_seen_state") for e in self.lanes):
@@ -133,10 +144,25 @@ class ContinuousBatcher:
 
     def submit(self, prompt_ids: Sequence[int], max_new: int,
                sampler: Optional[Sampler] = None,
-               eos_id: Optional[int] = None) -> Request:
+               eos_id: Optional[int] = None,
+               logprobs: Optional[int] = None) -> Request:
         """Raises ValueError (before any slot is taken) on an invalid or
         oversized request — the caller can reject it (HTTP 422) without
-        the decode loop ever seeing it."""
+        the decode loop ever seeing it.
+
+        logprobs: None = off; n in 0..8 records, per generated token, its
+        log-probability under the raw logits (`Request.out_logprobs`) and
+        the n most likely tokens with theirs (`Request.out_top`) — the
+        semantics of `engine.sampler.logprobs_reference`, independent of
+        the sampler settings. Needs an engine with `logprobs()`."""
+        if logprobs is not None:
+            if isinstance(logprobs, bool) or not isinstance(logprobs, int) \
+                    or not 0 <= logprobs <= LOGPROBS_MAX_TOP:
+                raise ValueError(
+                    f"logprobs must be an integer in 0..{LOGPROBS_MAX_TOP}")
+            if not all(hasattr(e, "logprobs") for e in self.lanes):
+                raise ValueError("logprobs needs an engine with logprobs()")
+            self._logprobs_seen = True
         if len(prompt_ids) < 1:
             raise ValueError("prompt must contain at least one token")
         if max_new < 1:
@@ -148,7 +174,8 @@ class ContinuousBatcher:
                 f"exceeds n_ctx={n_ctx}")
         r = Request(rid=self._next_rid, prompt=list(map(int, prompt_ids)),
                     max_new=max_new, sampler=sampler,
-                    eos_id=self.eos_id if eos_id is None else eos_id)
+                    eos_id=self.eos_id if eos_id is None else eos_id,
+                    logprobs=logprobs)
         self._next_rid += 1
         self.queue.append(r)
         return r
@@ -288,13 +315,18 @@ class ContinuousBatcher:
                 if self.device_sampling:
                     sampled_ids = self._sample_lane(eng, j, lg, reqs,
                                                     lane_slots, drafts)
-            work.append((reqs, drafts, greedy_ids, lg, sampled_ids))
+                lp = None
+                if self._logprobs_seen and any(r.logprobs is not None
+                                               for r in reqs):
+                    lp = self._logprobs_lane(eng, lg, reqs, drafts,
+                                             greedy_ids, sampled_ids)
+            work.append((reqs, drafts, greedy_ids, lg, sampled_ids, lp))
         if self._streams is not None:
             for st in self._streams:
                 torch.cuda.current_stream().wait_stream(st)
 
         finished: List[Request] = []
-        for reqs, drafts, greedy_ids, lg, sampled_ids in work:
+        for reqs, drafts, greedy_ids, lg, sampled_ids, lp in work:
             if greedy_ids is not None and greedy_ids.device.type != "cpu":
                 greedy_ids = greedy_ids.cpu()
             lg_host = None
@@ -303,8 +335,16 @@ class ContinuousBatcher:
                     sampled_ids = sampled_ids.cpu().tolist()
             elif any(r.sampler is not None for r in reqs):
                 lg_host = lg.float().cpu().numpy()
+            if lp is not None:
+                # the launch was queued behind the ids on the lane's
+                # stream: this copy waits for nothing the id copy above
+                # did not already wait for
+                packed, n, first = lp
+                a = packed.cpu().numpy()
+                lp = (a[:, 0].tolist(), a[:, 1:1 + n].tolist(),
+                      a[:, 1 + n:].copy().view("int32").tolist(), first)
             self._advance(reqs, drafts, greedy_ids, lg_host, finished,
-                          sampled_ids)
+                          sampled_ids, lp)
         return finished
 
     def _is_greedy(self, r: Request) -> bool:
@@ -332,6 +372,51 @@ class ContinuousBatcher:
         return eng.sample(lg, rows, slots, u, temp, pen, top_k, top_p,
                           self._seen[j])
 
+    def _logprobs_lane(self, eng, lg, reqs, drafts, greedy_ids,
+                       sampled_ids):
+        """One engine.logprobs call for the lane's requests that asked
+        and whose token was chosen on the engine (argmax or device
+        sample); the chosen ids are gathered on the device. Returns
+        (packed [R, 1 + 2n] device tensor: lp ‖ top_lp ‖ top_ids bits, n,
+        {request index: its first packed row}), or None when every asker
+        is host-sampled (those are served from the host logits)."""
+        n_greedy = 0 if greedy_ids is None else int(greedy_ids.shape[0])
+        rows, src, first = [], [], {}
+        row = 0
+        n_sampled = 0
+        top_n = 0
+        for qi, (r, d) in enumerate(zip(reqs, drafts)):
+            greedy = self._is_greedy(r)
+            if r.logprobs is not None and (greedy or self.device_sampling):
+                first[qi] = len(rows)
+                top_n = max(top_n, r.logprobs)
+                if greedy:
+                    # all 1 + len(draft) rows: row + i holds the token
+                    # _advance emits for accepted position i
+                    span = range(row, row + 1 + len(d))
+                    rows += span
+                    src += span
+                else:
+                    rows.append(row)
+                    src.append(n_greedy + n_sampled)
+            if not greedy and self.device_sampling:
+                n_sampled += 1
+            row += 1 + len(d)
+        if not rows:
+            return None
+        parts = [t for t in (greedy_ids, sampled_ids) if t is not None]
+        ids = parts[0] if len(parts) == 1 else torch.cat(parts)
+        if src != list(range(int(ids.shape[0]))):
+            ids = ids.index_select(0, torch.tensor(
+                src, dtype=torch.int32, device=ids.device))
+        lp, top_ids, top_lp = eng.logprobs(lg, rows, ids, top_n)
+        if top_n:
+            lp = torch.cat([lp.unsqueeze(1), top_lp,
+                            top_ids.view(torch.float32)], dim=1)
+        else:
+            lp = lp.unsqueeze(1)
+        return lp, top_n, first
+
     def _draft(self, r: Request) -> List[int]:
         """Prompt-lookup draft for a greedy request (possibly empty)."""
         if (self.spec_k <= 0 or self.spec_ngram <= 0 or
@@ -345,11 +430,17 @@ class ContinuousBatcher:
         return lookup_draft(r.prompt + r.out, self.spec_ngram, k)
 
     def _advance(self, reqs, drafts, greedy_ids, lg_host,
-                 finished, sampled_ids=None) -> None:
+                 finished, sampled_ids=None, lp=None) -> None:
         row = 0
         n_sampled = 0
-        for r, draft in zip(reqs, drafts):
+        for qi, (r, draft) in enumerate(zip(reqs, drafts)):
             nrows = 1 + len(draft)
+            rec = None   # per emitted token: (lp, top ids, top lps)
+            if lp is not None and r.logprobs is not None and \
+                    qi in lp[3]:
+                f = lp[3][qi]
+                rec = [(lp[0][f + i], lp[2][f + i], lp[1][f + i])
+                       for i in range(nrows)]
             if self.device_sampling and r.sampler is not None:
                 if r.sampler.greedy:
                     tid = int(greedy_ids[row])
@@ -360,6 +451,11 @@ class ContinuousBatcher:
                 emit = [tid]
             elif r.sampler is not None:
                 emit = [r.sampler(lg_host[row])]
+                if r.logprobs is not None:
+                    # the row is on the host already: no device launch
+                    v, top_ids, top_lp = logprobs_reference(
+                        lg_host[row], emit[0], r.logprobs)
+                    rec = [(v, top_ids.tolist(), top_lp.tolist())]
             else:
                 nxt = [int(greedy_ids[row + i]) for i in range(nrows)]
                 acc = 0
@@ -367,9 +463,14 @@ class ContinuousBatcher:
                     acc += 1
                 emit = nxt[:acc + 1]   # verified greedy continuations
             row += nrows
-            for tid in emit:
+            for i, tid in enumerate(emit):
                 self.tokens_out += 1
                 r.out.append(tid)
+                if rec is not None:
+                    v, top_ids, top_lp = rec[i]
+                    r.out_logprobs.append(v)
+                    r.out_top.append(list(zip(top_ids[:r.logprobs],
+                                              top_lp[:r.logprobs])))
                 r._next_tok = tid
                 r._pos += 1
                 if len(r.out) >= r.max_new or (r.eos_id is not None and

@@ -57,6 +57,10 @@ def main():
                     help="sample on the GPU (one batched launch per lane "
                          "and step) instead of the per-request host "
                          "Sampler over logits copied to the host")
+    ap.add_argument("--logprobs", type=int, default=None,
+                    help="ask for per-token log-probabilities with this "
+                         "many top alternatives (0..8) on every request "
+                         "(default: off)")
     args = ap.parse_args()
     if args.device_sampling and args.temperature is None:
         ap.error("--device-sampling needs --temperature")
@@ -87,7 +91,8 @@ def main():
 
     reqs = [bat.submit(torch.randint(3, hp.n_vocab, (args.prompt_len,),
                                      generator=g).tolist(),
-                       args.num_tokens, sampler=sampler())
+                       args.num_tokens, sampler=sampler(),
+                       logprobs=args.logprobs)
             for _ in range(args.requests)]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -112,7 +117,7 @@ def main():
                 reqs.append(bat.submit(
                     torch.randint(3, hp.n_vocab, (args.long_prompt,),
                                   generator=g).tolist(), args.num_tokens,
-                    sampler=sampler()))
+                    sampler=sampler(), logprobs=args.logprobs))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     total = sum(len(r.out) for r in reqs)
@@ -122,6 +127,10 @@ def main():
         f"sampled on {'device' if args.device_sampling else 'host'} "
         f"T={args.temperature} rp={args.repeat_penalty} "
         f"top_k={args.top_k} top_p={args.top_p}")
+    mode += (", logprobs off" if args.logprobs is None
+             else f", logprobs on (top {args.logprobs})")
+    if args.logprobs is not None:
+        assert all(len(r.out_logprobs) == len(r.out) for r in reqs)
     print(f"[{mode}] "
           f"{args.requests} requests x {args.num_tokens} new tokens "
           f"(prompt {args.prompt_len}, {bat.n_slots} slots on "
