@@ -644,9 +644,198 @@ class SliceEngine {
     torch::Tensor final_norm_, final_normprep_;
 };
 
+// ------------------------------------------------------------ test hooks
+// Direct entry points to the attention launchers for tests/
+// test_gpu_attention.py. NOT serving API: they allocate per call, sync the
+// host to validate pos/seq, and exist so each kernel can be compared with
+// a float64 reference on its own. Every argument that could send a kernel
+// out of bounds is refused here.
+
+struct AttnDims {
+    int T, H, Hkv, D, E, Ekv, ctx, slots;
+};
+
+torch::Tensor check_f16_store(const torch::Tensor& t, const AttnDims& d,
+                              const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 1 &&
+                    t.scalar_type() == torch::kFloat16,
+                name, " must be a flat contiguous f16 device tensor");
+    // the engine's own allocation rule: the 16-half pad is mandatory
+    // (load_voct reads whole octets past the last head)
+    TORCH_CHECK(t.numel() == (int64_t)d.slots * d.ctx * d.Ekv + 16, name,
+                " must hold exactly n_slots*n_ctx*Ekv + 16 halves");
+    return t;
+}
+
+AttnDims check_attn_args(int64_t T, int64_t n_head, int64_t n_head_kv,
+                         int64_t head_dim, int64_t n_ctx, int64_t n_slots,
+                         const torch::Tensor& k_store,
+                         const torch::Tensor& v_store,
+                         const torch::Tensor& pos,
+                         const torch::Tensor& seq) {
+    TORCH_CHECK(T >= 1 && T <= 4096, "token count out of range");
+    TORCH_CHECK(n_head >= 1 && n_head_kv >= 1 && n_head <= 1024 &&
+                    n_head % n_head_kv == 0,
+                "n_head must be a positive multiple of n_head_kv");
+    TORCH_CHECK(head_dim >= 2 && head_dim % 2 == 0 && head_dim <= 128,
+                "head_dim must be even and <= 128");
+    TORCH_CHECK(n_ctx >= 1 && n_slots >= 1 &&
+                    n_ctx * n_slots <= ((int64_t)1 << 24),
+                "n_ctx/n_slots out of range");
+    AttnDims d;
+    d.T = (int)T;
+    d.H = (int)n_head;
+    d.Hkv = (int)n_head_kv;
+    d.D = (int)head_dim;
+    d.E = d.H * d.D;
+    d.Ekv = d.Hkv * d.D;
+    d.ctx = (int)n_ctx;
+    d.slots = (int)n_slots;
+    TORCH_CHECK(d.E % 16 == 0 && d.Ekv % 16 == 0,
+                "E and Ekv must be multiples of 16");
+    check_f16_store(k_store, d, "k_store");
+    check_f16_store(v_store, d, "v_store");
+    check_i32(pos, "pos");
+    check_i32(seq, "seq");
+    TORCH_CHECK(pos.dim() == 1 && seq.dim() == 1 && pos.numel() == T &&
+                    seq.numel() == T,
+                "pos and seq must be [T]");
+    // host-side range check (a sync is fine in a test hook)
+    TORCH_CHECK(pos.min().item<int64_t>() >= 0 &&
+                    pos.max().item<int64_t>() < n_ctx,
+                "pos out of [0, n_ctx)");
+    TORCH_CHECK(seq.min().item<int64_t>() >= 0 &&
+                    seq.max().item<int64_t>() < n_slots,
+                "seq out of [0, n_slots)");
+    return d;
+}
+
+using AttnResult = std::tuple<torch::Tensor, torch::Tensor, int64_t>;
+
+// (out [T, E] f32, zero-filled out_prep i16 [(E/8)*jtw*128], jtw)
+AttnResult alloc_attn_result(const AttnDims& d) {
+    auto dev = torch::TensorOptions().device(torch::kCUDA);
+    const int jtw = jt_width(d.T);
+    TORCH_CHECK(jtw * 16 >= d.T, "jt_width does not cover T");
+    auto out = torch::zeros({d.T, d.E}, dev.dtype(torch::kFloat32));
+    auto prep = torch::zeros({(int64_t)(d.E / 8) * jtw * 128},
+                             dev.dtype(torch::kInt16));
+    return {out, prep, (int64_t)jtw};
+}
+
+const __half* h16c(const torch::Tensor& t) {
+    return reinterpret_cast<const __half*>(t.data_ptr());
+}
+__half* h16(torch::Tensor& t) {
+    return reinterpret_cast<__half*>(t.data_ptr());
+}
+
+AttnDims check_q_args(const torch::Tensor& q, int64_t n_head,
+                      int64_t n_head_kv, int64_t n_ctx, int64_t n_slots,
+                      const torch::Tensor& k_store,
+                      const torch::Tensor& v_store,
+                      const torch::Tensor& pos, const torch::Tensor& seq) {
+    check_f32(q, "q");
+    TORCH_CHECK(q.dim() == 2 && q.size(0) >= 1, "q must be [T, E]");
+    TORCH_CHECK(n_head >= 1 && q.size(1) % n_head == 0,
+                "E not divisible by n_head");
+    return check_attn_args(q.size(0), n_head, n_head_kv,
+                           q.size(1) / n_head, n_ctx, n_slots, k_store,
+                           v_store, pos, seq);
+}
+
+AttnResult attention_decode(torch::Tensor q, torch::Tensor k_store,
+                            torch::Tensor v_store, torch::Tensor pos,
+                            torch::Tensor seq, int64_t n_head,
+                            int64_t n_head_kv, int64_t n_ctx,
+                            int64_t n_slots) {
+    const AttnDims d = check_q_args(q, n_head, n_head_kv, n_ctx, n_slots,
+                                    k_store, v_store, pos, seq);
+    AttnResult r = alloc_attn_result(d);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    launch_attention(s, q.data_ptr<float>(), h16c(k_store), h16(v_store),
+                     std::get<0>(r).data_ptr<float>(), u16p(std::get<1>(r)),
+                     pos.data_ptr<int>(), seq.data_ptr<int>(), d.T, d.H,
+                     d.E, d.Ekv, d.D, d.ctx, nullptr, 0, nullptr);
+    return r;
+}
+
+// appends row pos[t] of slot seq[t] to k_store / v_store in place
+AttnResult attention_decode_fused(torch::Tensor slab, torch::Tensor k_store,
+                                  torch::Tensor v_store, torch::Tensor pos,
+                                  torch::Tensor seq, torch::Tensor inv_freq,
+                                  int64_t n_head, int64_t n_head_kv,
+                                  int64_t head_dim, int64_t n_ctx,
+                                  int64_t n_slots) {
+    check_i32(pos, "pos");
+    const int64_t T = pos.numel();
+    TORCH_CHECK(T <= kMaxTokens, "the fused variant takes at most ",
+                kMaxTokens, " tokens (slab token width)");
+    const AttnDims d = check_attn_args(T, n_head, n_head_kv, head_dim,
+                                       n_ctx, n_slots, k_store, v_store,
+                                       pos, seq);
+    // every block appends its own row and reads only its own sequence
+    auto sorted = std::get<0>(seq.to(torch::kCPU).to(torch::kInt64).sort());
+    for (int64_t i = 1; i < T; ++i)
+        TORCH_CHECK(sorted[i].item<int64_t>() !=
+                        sorted[i - 1].item<int64_t>(),
+                    "seq values must be pairwise distinct");
+    const int ks = qkv16_ks(d.E, d.Ekv);
+    check_f32(slab, "slab");
+    TORCH_CHECK(slab.numel() == (int64_t)((d.E + 2 * d.Ekv) / 16) * ks *
+                                    kMaxTokens * 16,
+                "slab must be f32[(E+2Ekv)/16][ks][64][16]");
+    check_f32(inv_freq, "inv_freq");
+    TORCH_CHECK(inv_freq.numel() == d.D / 2, "inv_freq must be [D/2]");
+    AttnResult r = alloc_attn_result(d);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    launch_attention(s, nullptr, h16c(k_store), h16(v_store),
+                     std::get<0>(r).data_ptr<float>(), u16p(std::get<1>(r)),
+                     pos.data_ptr<int>(), seq.data_ptr<int>(), d.T, d.H,
+                     d.E, d.Ekv, d.D, d.ctx, slab.data_ptr<float>(), ks,
+                     inv_freq.data_ptr<float>());
+    return r;
+}
+
+AttnResult attention_prefill(torch::Tensor q, torch::Tensor k_store,
+                             torch::Tensor v_store, torch::Tensor pos,
+                             torch::Tensor seq, int64_t n_head,
+                             int64_t n_head_kv, int64_t n_ctx,
+                             int64_t n_slots) {
+    const AttnDims d = check_q_args(q, n_head, n_head_kv, n_ctx, n_slots,
+                                    k_store, v_store, pos, seq);
+    AttnResult r = alloc_attn_result(d);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    launch_attn_prefill(s, q.data_ptr<float>(), h16c(k_store),
+                        h16c(v_store), std::get<0>(r).data_ptr<float>(),
+                        u16p(std::get<1>(r)), pos.data_ptr<int>(),
+                        seq.data_ptr<int>(), d.T, d.H, d.E, d.Ekv, d.D,
+                        d.ctx);
+    return r;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    // test hooks (see above), not serving API
+    m.def("attention_decode", &attention_decode, py::arg("q"),
+          py::arg("k_store"), py::arg("v_store"), py::arg("pos"),
+          py::arg("seq"), py::arg("n_head"), py::arg("n_head_kv"),
+          py::arg("n_ctx"), py::arg("n_slots"));
+    m.def("attention_decode_fused", &attention_decode_fused,
+          py::arg("slab"), py::arg("k_store"), py::arg("v_store"),
+          py::arg("pos"), py::arg("seq"), py::arg("inv_freq"),
+          py::arg("n_head"), py::arg("n_head_kv"), py::arg("head_dim"),
+          py::arg("n_ctx"), py::arg("n_slots"));
+    m.def("attention_prefill", &attention_prefill, py::arg("q"),
+          py::arg("k_store"), py::arg("v_store"), py::arg("pos"),
+          py::arg("seq"), py::arg("n_head"), py::arg("n_head_kv"),
+          py::arg("n_ctx"), py::arg("n_slots"));
+    m.def("qkv16_ks", [](int64_t E, int64_t Ekv) {
+        return (int64_t)qkv16_ks((int)E, (int)Ekv);
+    }, py::arg("E"), py::arg("Ekv"));
+    m.def("jt_width", [](int64_t T) { return (int64_t)jt_width((int)T); },
+          py::arg("T"));
     m.doc() = "MI355X-native layer-slice inference engine (CDNA4 HIP kernels)";
     py::class_<SliceEngine, std::shared_ptr<SliceEngine>>(m, "SliceEngine")
         .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
