@@ -35,6 +35,7 @@ constexpr int kMaxTokens = 64;  // per-forward token cap (4 MFMA col tiles)
 
 // Tail slack appended to every MFMA-path allocation: the pipelined K loop
 // prefetches ONE load batch past its range (mfma_gemm.hip wave_tile_kloop).
+// engine/repack.py TAIL_SLACK_* are the Python side of the first four.
 constexpr int64_t kTailSlackQ = 256;     // int32 elements (1 KiB)
 constexpr int64_t kTailSlackQ8 = 512;    // int32 elements (byte stream)
 constexpr int64_t kTailSlackAB = 128;    // f16 elements (256 B)
@@ -592,9 +593,7 @@ class SliceEngine {
     int64_t max_prefill() const { return maxP_; }
     int64_t n_ctx() const { return ctx_; }
     int64_t max_batch() const { return B_; }
-    // the per-layer KV tensors ([L, B, ctx, E] f16); exposed so the
-    // Python prefill fast path (slice_engine.forward large-T branch)
-    // can append rows the kernel decode path then attends over
+    // the per-layer KV tensors ([L, B, ctx, E] f16)
     torch::Tensor k_cache() const { return k_cache_; }
     torch::Tensor v_cache() const { return v_cache_; }
 

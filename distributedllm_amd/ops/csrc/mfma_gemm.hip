@@ -27,7 +27,7 @@
 // w2_mt.
 //
 // Weight layout in HBM (repacked at load; python side in
-// engine/slice_engine.py::repack_mfma), R = rows/16 row tiles:
+// engine/repack.py::repack_mfma), R = rows/16 row tiles:
 //   q4   : data   u32[R][nbp/4][4 ws][16 i][4 kb]  (one dwordx4 per lane
 //          covers 4 consecutive K-blocks; nbp = nb padded to 4)
 //          scales f16 (alpha, beta)[R][nbp/4][16 i][4 kb]

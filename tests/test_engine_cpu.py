@@ -85,19 +85,22 @@ class TestTorchEngineParity:
         assert torch.allclose(lg, lg_ref, atol=1e-3)
 
 
+
+
 def test_byte_quant_repack_values_exact():
     """The W_Q8B repack's re-biased bytes must reconstruct the codec's
     dequantized weights exactly: w = alpha*(u - 128) + beta (the GPU
     kernel computes the same quantity in packed f16)."""
     import numpy as np
-    from distributedllm_amd.engine.slice_engine import _byte_values
+    from distributedllm_amd.engine.repack import expand_byte_quant
     from distributedllm_amd.formats import ggml, synthetic
     for ft in (ggml.FTYPE_MOSTLY_Q5_0, ggml.FTYPE_MOSTLY_Q5_1,
                ggml.FTYPE_MOSTLY_Q8_0):
         f = synthetic.build_model("tiny", seed=0, ftype=ft)
         t = next(x for x in f.tensors
                  if x.name.endswith("attention.wq.weight"))
-        vals, alpha, beta = _byte_values(t)
+        vals, alpha, beta = (x.numpy() for x in expand_byte_quant(t, "cpu"))
+        assert vals.dtype == np.uint8 and alpha.dtype == np.float32
         w = (alpha[..., None] * (vals.astype(np.float32) - 128.0) +
              beta[..., None])
         ref = t.to_f32().reshape(w.shape[0], -1, 32)
@@ -110,17 +113,29 @@ def test_detile_inverts_repack():
     CPU tensors) then detile reproduces the codec's dequantized weights
     (f16-rounded) — this is the CPU-side proof that the layouts the
     prefill/decode kernels stream carry the exact quantized values."""
-    import numpy as np
     import torch
-    from distributedllm_amd.engine.slice_engine import (
-        detile_mfma, repack_mfma)
+    import repack_cases as RC
+    from distributedllm_amd.engine.repack import detile_mfma, repack_mfma
     from distributedllm_amd.formats import ggml, synthetic
+    tensors = []
     for ft in (ggml.FTYPE_MOSTLY_Q4_0, ggml.FTYPE_MOSTLY_Q4_1,
                ggml.FTYPE_MOSTLY_Q8_0, ggml.FTYPE_MOSTLY_Q5_0,
                ggml.FTYPE_MOSTLY_Q5_1, ggml.FTYPE_MOSTLY_F16):
         f = synthetic.build_model("tiny", seed=1, ftype=ft)
-        t = next(x for x in f.tensors
-                 if x.name.endswith("feed_forward.w1.weight"))
+        tensors += [x for x in f.tensors
+                    if x.name == "layers.0.feed_forward.w1.weight"]
+    # k-quants (W_Q8B per-32 and the W_Q8B16 two-plane form): E = 512
+    # and F = 1536 columns, i.e. 2 and 6 super-blocks per row
+    for ft in (ggml.FTYPE_MOSTLY_Q2_K, ggml.FTYPE_MOSTLY_Q3_K_M,
+               ggml.FTYPE_MOSTLY_Q4_K_M, ggml.FTYPE_MOSTLY_Q5_K_M,
+               ggml.FTYPE_MOSTLY_Q6_K):
+        f = RC._model("small_k", 8, ft)
+        tensors += [x for x in f.tensors if x.name in (
+            "layers.0.attention.wq.weight",
+            "layers.0.feed_forward.w1.weight",
+            "layers.0.feed_forward.w2.weight")]
+    assert len(tensors) == 6 + 5 * 3
+    for t in tensors:
         rows, cols = t.shape_rows_cols
         mat = repack_mfma(t, "cpu")
         got = detile_mfma(mat, rows, cols).float()
@@ -130,74 +145,34 @@ def test_detile_inverts_repack():
         # rounding at repack
         tol = 4e-3 * want.abs().max().item() + 1e-6
         err = (got - want).abs().max().item()
-        assert err <= tol, (ggml.TYPE_NAMES[ggml._FTYPE_TO_GGML[ft]], err)
+        assert err <= tol, (ggml.TYPE_NAMES[t.gtype], t.name, err, tol)
+
+
+def _check_group(group):
+    """repack_mfma on the CPU == the golden tiles, bit for bit
+    (tests/repack_cases.py says where the digests come from)."""
+    import repack_cases as RC
+    from distributedllm_amd.engine.repack import repack_mfma
+    for case_id, t in RC.cases(group):
+        RC.check(case_id, t, repack_mfma(t, "cpu"))
 
 
 def test_torch_q4_repack_matches_numpy():
-    """The GPU-side torch q4 repack (one H2D of compressed bytes, bit
-    work on device) must produce bit-identical tiles/scales to the
-    numpy reference path."""
-    import numpy as np
-    import torch
-    from distributedllm_amd.engine import slice_engine as SE
-    from distributedllm_amd.formats import ggml, synthetic
-    for ft in (ggml.FTYPE_MOSTLY_Q4_0, ggml.FTYPE_MOSTLY_Q4_1):
-        f = synthetic.build_model("small", seed=3, ftype=ft)
-        t = next(x for x in f.tensors
-                 if x.name.endswith("attention.wq.weight"))
-        d_np, s_np, wt_np = SE.repack_mfma(t, "cpu")       # numpy path
-        d_th, s_th, wt_th = SE._repack_q4_torch(t, "cpu")  # torch ops
-        assert wt_np == wt_th
-        assert torch.equal(d_np, d_th)
-        assert torch.equal(s_np.view(torch.int16), s_th.view(torch.int16))
+    _check_group("q4")
 
 
 def test_torch_byte_repack_matches_numpy():
-    """Torch q5_0/q5_1/q8_0 byte-stream repack == numpy path, bit for
-    bit (same contract as the q4 port)."""
-    import torch
-    from distributedllm_amd.engine import slice_engine as SE
-    from distributedllm_amd.formats import ggml, synthetic
-    for ft in (ggml.FTYPE_MOSTLY_Q5_0, ggml.FTYPE_MOSTLY_Q5_1,
-               ggml.FTYPE_MOSTLY_Q8_0):
-        f = synthetic.build_model("small", seed=5, ftype=ft)
-        t = next(x for x in f.tensors
-                 if x.name.endswith("attention.wq.weight"))
-        d_np, s_np, wt_np = SE.repack_mfma(t, "cpu")        # numpy path
-        d_th, s_th, wt_th = SE._repack_byte_torch(t, "cpu")
-        assert wt_np == wt_th
-        assert torch.equal(d_np, d_th), ggml.TYPE_NAMES[t.gtype]
-        assert torch.equal(s_np.view(torch.int16), s_th.view(torch.int16))
+    _check_group("byte")
 
 
 def test_torch_f16_repack_matches_numpy():
-    import torch
-    from distributedllm_amd.engine import slice_engine as SE
-    from distributedllm_amd.formats import ggml, synthetic
-    f = synthetic.build_model("small", seed=6, ftype=ggml.FTYPE_MOSTLY_F16)
-    t = next(x for x in f.tensors
-             if x.name.endswith("feed_forward.w1.weight"))
-    d_np, _, wt_np = SE.repack_mfma(t, "cpu")
-    d_th, _, wt_th = SE._repack_f16_torch(t, "cpu")
-    assert wt_np == wt_th
-    assert torch.equal(d_np.view(torch.int16), d_th.view(torch.int16))
+    _check_group("f16")
 
 
 def test_torch_kquant_repack_matches_numpy():
-    """Torch q2_K..q6_K super-block repack == numpy path, bit for bit."""
-    import torch
-    from distributedllm_amd.engine import slice_engine as SE
-    from distributedllm_amd.formats import ggml, synthetic
-    for ft in (ggml.FTYPE_MOSTLY_Q2_K, ggml.FTYPE_MOSTLY_Q3_K_M,
-               ggml.FTYPE_MOSTLY_Q4_K_M, ggml.FTYPE_MOSTLY_Q5_K_M,
-               ggml.FTYPE_MOSTLY_Q6_K):
-        f = synthetic.build_model("small_k", seed=8, ftype=ft)
-        for tname in ("attention.wq.weight", "feed_forward.w1.weight"):
-            t = next(x for x in f.tensors if x.name.endswith(tname))
-            d_np, s_np, wt_np = SE.repack_mfma(t, "cpu")    # numpy path
-            d_th, s_th, wt_th = SE._repack_kquant_torch(t, "cpu")
-            assert wt_np == wt_th
-            assert torch.equal(d_np, d_th), ggml.TYPE_NAMES[t.gtype]
-            assert torch.equal(s_np.view(torch.int16),
-                               s_th.view(torch.int16)), \
-                ggml.TYPE_NAMES[t.gtype]
+    _check_group("kquant")
+
+
+def test_repack_padded_k_blocks_match_golden():
+    """nb = 2 and nb = 3 padded to the 4-block load group."""
+    _check_group("padded")

@@ -111,13 +111,14 @@ def test_requantize_kquant_fallback():
 def test_kquant_byte_expansion_matches_codec():
     """The engine's byte expansion (repack input) must reproduce the
     codec's dequantized values exactly: w = alpha*(u-128) + beta."""
-    from distributedllm_amd.engine.slice_engine import (
-        _K16_GTYPES, _K32_GTYPES, _kquant_byte_values)
+    from distributedllm_amd.engine.repack import (
+        _K16_GTYPES, _K32_GTYPES, expand_kquant)
     x = RNG.standard_normal((16, 512)).astype(np.float32) * 0.1
     for gt in _K32_GTYPES + _K16_GTYPES:
         t = ggml.GGMLTensor.from_f32("w", x, gt)
         want = t.to_f32()
-        vals, alpha, beta = _kquant_byte_values(t)
+        vals, alpha, beta = (a.numpy() for a in expand_kquant(t, "cpu"))
+        assert vals.dtype == np.uint8 and alpha.dtype == np.float32
         u = vals.astype(np.float32) - 128.0
         if gt in _K32_GTYPES:
             got = alpha[..., None] * u + beta[..., None]

@@ -222,33 +222,17 @@ def test_quantize_edge_case_blocks_match_python(bins, tmp_path):
 
 
 def test_torch_repack_edge_case_bits(tmp_path):
-    """Same degenerate contents through the torch repack vs numpy repack
-    (inf/nan f16 scale patterns from random-byte files are also covered
-    by the GPU load bench; here we assert bit equality on the codec-
-    produced layouts)."""
-    import torch
-    from distributedllm_amd.engine import slice_engine as SE
-    from distributedllm_amd.formats import kquants
-    rows, cols = 16, 512
-    rng = np.random.default_rng(12)
-    w = (rng.standard_normal((rows, cols)) * 0.02).astype(np.float32)
-    w[0, :] = 0.0
-    w[3, :256] = 1e-42
-    w[4, :] = 3.0e4
-    for gt, quant in [
-            (ggml.GGML_TYPE_Q5_0, q4.quantize_q5_0),
-            (ggml.GGML_TYPE_Q8_0, q4.quantize_q8_0),
-            (ggml.GGML_TYPE_Q4_K, kquants.quantize_q4_K),
-            (ggml.GGML_TYPE_Q6_K, kquants.quantize_q6_K)]:
-        t = ggml.GGMLTensor(name="e", ne=(cols, rows), gtype=gt,
-                            raw=quant(w).tobytes())
-        d_np, s_np, wt_np = SE.repack_mfma(t, "cpu")
-        fn = (SE._repack_byte_torch
-              if gt in (ggml.GGML_TYPE_Q5_0, ggml.GGML_TYPE_Q8_0)
-              else SE._repack_kquant_torch)
-        d_th, s_th, wt_th = fn(t, "cpu")
-        assert wt_np == wt_th and torch.equal(d_np, d_th)
-        assert torch.equal(s_np.view(torch.int16), s_th.view(torch.int16))
+    """Same degenerate contents (all-zero row, subnormal amax, near
+    f16 max; q5_0, q8_0, q4_K, q6_K) through the repack: tiles, scales
+    and wtype equal the golden ones recorded from the numpy repack, bit
+    for bit (inf/nan f16 scale patterns from random-byte files are also
+    covered by the GPU load bench)."""
+    import repack_cases as RC
+    from distributedllm_amd.engine.repack import repack_mfma
+    cases = RC.cases("edge")
+    assert len(cases) == 4
+    for case_id, t in cases:
+        RC.check(case_id, t, repack_mfma(t, "cpu"))
 
 
 def test_pmc_summary_tool(tmp_path):
