@@ -354,7 +354,7 @@ class SliceEngine {
         (void)hipMemsetAsync(ssf, 0, sizeof(float) * L_ * ssw_, s);
         launch_prep_x(s, xp, xprep, ssa, E_, T);
         if (T > kMaxTokens) {
-            // large-M path: the *_mt kernels cover all T tokens in one
+            // large-M path: launch_*_mt cover all T tokens in one
             // launch per op (XCD-grouped token tiles), the whole layer
             // loop sequenced here in C++ — no host tiling, no library
             // GEMMs, q4 tiles read directly. Serves BOTH prompt prefill
@@ -392,14 +392,14 @@ class SliceEngine {
                                         T, H_, E_, EK_, D_, ctx_);
                 ck("attn", li);
                 launch_gemm16_mt(s, l.mo.w, aprep, xp, xprep,
-                                 ssf + li * ssw_, T, /*res_sq=*/1);
+                                 ssf + li * ssw_, T);
                 ck("wo", li);
                 launch_ffn16_mt(s, l.m1.w, l.m3.w, xprep,
                                 u16p(l.ffn_normprep), ssf + li * ssw_,
                                 eps_, gprep, T);
                 ck("ffn", li);
                 launch_gemm16_mt(s, l.m2.w, gprep, xp, xprep,
-                                 ssa + (li + 1) * ssw_, T, /*res_sq=*/1);
+                                 ssa + (li + 1) * ssw_, T);
                 ck("w2", li);
             }
             return x;

@@ -131,9 +131,11 @@ void launch_logprobs(hipStream_t s, const float* logits, const int* rows,
                      int R, int T, int V, int top_n);
 
 // ---------------------------------------------------------- prefill path
-// Large-M (T > 64) layer kernels: one launch covers all T tokens with an
+// Large-M (T > 64) layer launchers: one launch covers all T tokens with an
 // XCD-aware (row-tile x 64-token-group) grid. Side channels use the
-// jt_width(T) token-panel stride.
+// jt_width(T) token-panel stride. qkv and ffn run the decode templates
+// with the large-M flag, k_qkv16<…, true> and k_ffn16<…, true>; wo / w2
+// run k_gemm16_mt.
 int jt_width(int T);
 
 // Q-tiled (16 queries/block) matrix-core flash attention for prefill: each
@@ -154,10 +156,10 @@ void launch_qkv16_mt(hipStream_t s, const WMat2& wq, const WMat2& wk,
                      const float* inv_freq, int E, int Ekv, int D,
                      int n_ctx, int T);
 
+// wo / w2: y += w * b with the fused residual + sumsq + xprep epilogue
 void launch_gemm16_mt(hipStream_t s, const WMat2& w,
                       const unsigned short* bprep, float* y,
-                      unsigned short* xprep_out, float* ss_out, int T,
-                      int res_sq);
+                      unsigned short* xprep_out, float* ss_out, int T);
 
 void launch_ffn16_mt(hipStream_t s, const WMat2& w1, const WMat2& w3,
                      const unsigned short* xprep,

@@ -1,6 +1,7 @@
 // MFMA dequant-GEMM family of the slice engine (gfx950) — the production
 // path for every quantized / f16 layer, decode (T <= 64) and large-M
-// prefill / wide decode (`*_mt`, T > 64). Design notes with the
+// prefill / wide decode (T > 64: `k_qkv16<…, true>`, `k_ffn16<…, true>`,
+// `k_gemm16_mt`, behind the launch_*_mt launchers). Design notes with the
 // measurements that drove each choice: docs/kernels.md.
 //
 // Matrix cores do the FLOPs; the VALU only unpacks. One
@@ -23,8 +24,7 @@
 // RT=2 slab split-K whose finish is either k_qkv_finish or the attention
 // prologue), attention, wo (slab split-K + k_reduce_prep, or the fused
 // GM_RES_SQ epilogue when E/16 is odd), ffn gate (w1/w3 + SwiGLU), w2
-// (like wo). A prefill layer is 5: qkv_mt, attention, wo_mt, ffn_mt,
-// w2_mt.
+// (like wo). A prefill layer is 5: large-M qkv, attention, wo, ffn, w2.
 //
 // Weight layout in HBM (repacked at load; python side in
 // engine/repack.py::repack_mfma), R = rows/16 row tiles:
@@ -38,8 +38,9 @@
 //
 // Block = 4 waves; each wave owns a quarter of the K blocks of its row
 // tile(s); partial accumulators combine through LDS; wave 0 runs the
-// fused epilogue. A decode kernel and its `_mt` twin differ only in how a
-// block finds its (row tile, token tile).
+// fused epilogue. Decode and large-M differ only in how a block finds its
+// (row tile, token tile): k_qkv16 and k_ffn16 take that as the template
+// flag MTK; k_gemm16 / k_gemm16_mt stay two kernels (see k_gemm16_mt).
 //
 // Not to be changed casually: the bodies of wave_tile_kloop and
 // combine_acc, the grid decoders of the kernels, and — less obviously —
@@ -47,7 +48,10 @@
 // the K loop's pipeline was settled against SQ counters and the emitted
 // waits; merging kernels, turning template parameters into runtime
 // values, or refactoring an epilogue changes the K loop's code generation.
-// Compare per-kernel assembly and register counts before and after.
+// Compare per-kernel assembly and register counts before and after:
+// tools/kernel_isa_diff.py OLD.hip NEW.hip does that without a GPU.
+
+#include <type_traits>
 
 #include "device_common.h"
 #include "kernels.h"
@@ -168,7 +172,7 @@ __device__ __forceinline__ void a_frag_q8(uint32_t qA, uint32_t qB,
 // RT. acc[rt][n][jt][jj].
 // jtw/jt0: token-panel stride and first 16-token tile of this block in the
 // xprep side channel (layout [kc][jtw][16][8]). Decode callers pass
-// (JT, 0); the prefill *_mt kernels tile a T-wide panel with jtw = ceil(T/16)
+// (JT, 0); the large-M kernels tile a T-wide panel with jtw = ceil(T/16)
 // padded to the 4-tile group and jt0 = mtile*JT.
 template <int WT, bool NORM, int NM, int JT, int RT = 1, int PF = 4,
           int NW = NWAVES>
@@ -397,7 +401,7 @@ __device__ __forceinline__ void wave_tile_kloop(
         }
         // load_w ran nfull+1 times (the trailing prefetch) but only
         // nfull batches were consumed — rewind one batch so the tail
-        // loop reads the right K-blocks. (Latent until the prefill _mt
+        // loop reads the right K-blocks. (Latent until the large-M
         // kernels: 4-aligned q4 ranges never leave a tail, and the f16
         // slab kernels' per-wave ranges are < PF so nfull == 0.)
 #pragma unroll
@@ -486,9 +490,8 @@ __device__ __forceinline__ void combine_acc(float acc[NACC][4],
 // ---------------------------------------------------------- tile epilogues
 // Wave 0 holds the finished tile: lane (j = l&15, l>>4) owns the 4
 // consecutive rows [r0, r0+4), r0 = tile*16 + (l>>4)*4, of token column
-// t (j2 in the kernels: jt*16 + j for decode, (mtile*JT + jt)*16 + j for
-// the `_mt` twins — the global token index is all that differs between
-// the two epilogues of a pair).
+// t (j2 in the kernels: jt*16 + j in k_gemm16, (mtile*JT + jt)*16 + j in
+// k_gemm16_mt and in k_qkv16 / k_ffn16, whose decode half has mtile = 0).
 //
 // The epilogues share rope_rotate and slab_tile_store, but the q/k/v,
 // residual+sumsq+xprep and SwiGLU->gprep bodies stay written out in each
@@ -498,8 +501,9 @@ __device__ __forceinline__ void combine_acc(float acc[NACC][4],
 // This is deliberate: hipcc runs its early scalar passes on a kernel
 // BEFORE always-inline helpers are expanded, and moving these bodies or
 // that arithmetic behind a call changed register allocation and the
-// schedule INSIDE wave_tile_kloop (k_ffn16_mt went from 92 to 120 VGPRs,
-// occupancy 4 -> 3). Re-check the K loop's assembly before factoring them.
+// schedule INSIDE wave_tile_kloop (the large-M k_ffn16 went from 92 to 120
+// VGPRs, occupancy 4 -> 3). Re-check the K loop's assembly before factoring
+// them.
 
 // Split-K partial store: the lane's 4 rows of one token column into its
 // slot of a slab tile (f32[64 tok][16 rows]: dst = tile + tok*16 +
@@ -701,121 +705,6 @@ __global__ __launch_bounds__(BLOCK) void k_gemm16(
     }
 }
 
-// ------------------------------------------------------------- k_qkv16
-// QKV projections on MFMA + fused input RMSNorm + RoPE + KV append.
-// GQA: wk/wv have Ekv = Hkv*D rows (< E); KV cache rows are Ekv wide.
-// Tile space is [0, E/16) for wq then [.., +Ekv/16) each for wk/wv.
-template <int WT, int JT, int RT = 1>
-__global__ __launch_bounds__(BLOCK) void k_qkv16(
-    WMat2 wq, WMat2 wk, WMat2 wv, const unsigned short* __restrict__ xprep,
-    const unsigned short* __restrict__ normprep,
-    const float* __restrict__ ss_in, float eps, float* __restrict__ q_buf,
-    __half* __restrict__ k_cache, __half* __restrict__ v_cache,
-    const int* __restrict__ pos, const int* __restrict__ seq,
-    const float* __restrict__ inv_freq, int E, int Ekv, int D, int n_ctx,
-    int T) {
-    const int tq = (E >> 4) / RT;
-    const int tk = (Ekv >> 4) / RT;
-    const int mat = (blockIdx.x < tq) ? 0
-                    : (blockIdx.x < tq + tk) ? 1 : 2;
-    const int tile = blockIdx.x - ((mat == 0) ? 0 : (mat == 1) ? tq
-                                                               : tq + tk);
-    const WMat2& w = (mat == 0) ? wq : (mat == 1) ? wk : wv;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int j = lane & 15;
-    float acc[RT][1][JT][4];
-    const WMat2* ws[1] = {&w};
-    const int nbe = (WT == W_F16) ? (E >> 5) : (((E >> 5) + 3) & ~3);
-    wave_tile_kloop<WT, true, 1, JT, RT>(ws, tile, xprep, normprep, ss_in,
-                                         eps, acc, 0, nbe);
-    __shared__ float lds[3 * 64 * 4 * RT * JT];
-    combine_acc<RT * JT>(reinterpret_cast<float(*)[4]>(acc), lds);
-    if (threadIdx.x >= WAVE) return;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-    const int r0 = (tile * RT + rt) * 16 + (lane >> 4) * 4;
-#pragma unroll
-    for (int jt = 0; jt < JT; ++jt) {
-        const int j2 = jt * 16 + j;
-        if (j2 >= T) continue;
-        const int p = pos[j2];
-        if (mat == 2) {  // V rows: straight f16 cache append
-            __half* dst =
-                v_cache + ((size_t)seq[j2] * n_ctx + p) * Ekv + r0;
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-                dst[jj] = __float2half(acc[rt][0][jt][jj]);
-            continue;
-        }
-        // q/k: RoPE on in-lane pairs (rows r0+2q2, r0+2q2+1)
-#pragma unroll
-        for (int q2 = 0; q2 < 2; ++q2) {
-            const int e = r0 + 2 * q2;
-            const int d = e % D;
-            const float theta = (float)p * inv_freq[d >> 1];
-            float sn, cs;
-            __sincosf(theta, &sn, &cs);
-            float o0, o1;
-            rope_rotate(acc[rt][0][jt][2 * q2], acc[rt][0][jt][2 * q2 + 1],
-                        sn, cs, o0, o1);
-            if (mat == 0) {
-                q_buf[(size_t)j2 * E + e] = o0;
-                q_buf[(size_t)j2 * E + e + 1] = o1;
-            } else {
-                __half* dst =
-                    k_cache + ((size_t)seq[j2] * n_ctx + p) * Ekv + e;
-                dst[0] = __float2half(o0);
-                dst[1] = __float2half(o1);
-            }
-        }
-    }
-    }
-}
-
-// ------------------------------------------------------------- k_ffn16
-// w1 + w3 against the same B panel + fused input RMSNorm + SwiGLU; emits
-// the gate product straight into gprep (f16 B-layout over F).
-template <int WT, int JT, int RT = 1>
-__global__ __launch_bounds__(BLOCK) void k_ffn16(
-    WMat2 w1, WMat2 w3, const unsigned short* __restrict__ xprep,
-    const unsigned short* __restrict__ normprep,
-    const float* __restrict__ ss_in, float eps,
-    unsigned short* __restrict__ gprep, int T) {
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int j = lane & 15;
-    float acc[RT][2][JT][4];
-    const WMat2* ws[2] = {&w1, &w3};
-    const int nbf = (WT == W_F16) ? (w1.cols >> 5)
-                                  : (((w1.cols >> 5) + 3) & ~3);
-    wave_tile_kloop<WT, true, 2, JT, RT>(ws, blockIdx.x, xprep, normprep,
-                                         ss_in, eps, acc, 0, nbf);
-    __shared__ float lds[3 * 64 * 4 * RT * 2 * JT];
-    combine_acc<RT * 2 * JT>(reinterpret_cast<float(*)[4]>(acc), lds);
-    if (threadIdx.x >= WAVE) return;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-        const int r0 = (blockIdx.x * RT + rt) * 16 + (lane >> 4) * 4;
-#pragma unroll
-        for (int jt = 0; jt < JT; ++jt) {
-            const int j2 = jt * 16 + j;
-            if (j2 >= T) continue;
-            float g[4];
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                const float v1 = acc[rt][0][jt][jj];
-                const float silu = v1 / (1.0f + __expf(-v1));
-                g[jj] = silu * acc[rt][1][jt][jj];
-            }
-            uint2 o;
-            o.x = pack_f16(g[0], g[1]);
-            o.y = pack_f16(g[2], g[3]);
-            *reinterpret_cast<uint2*>(
-                gprep + (((size_t)(r0 >> 3) * JT + jt) * 16 + j) * 8 +
-                (r0 & 7)) = o;
-        }
-    }
-}
-
 // ------------------------------------------------------ slab qkv variant
 // For models whose qkv tile count underfills the chip (3B: 600 tiles),
 // the fused kernel runs at ~2.3 blocks/CU with the full B panel re-read
@@ -948,40 +837,63 @@ __global__ void k_qkv_finish(const float* __restrict__ slab, int ks,
 // re-served to the other groups from that XCD's L2 (blockIdx -> XCD is
 // round-robin on dispatch order, 8 XCDs).
 //
-// Returns (gtile, mtile); gtile may be >= GT (pad block -> caller exits).
-__device__ __forceinline__ void xcd_decode(int GT, int MT, int& gtile,
-                                           int& mtile) {
+// Returns (gtile, mtile); gtile may be past the last row tile (pad block
+// -> caller exits).
+__device__ __forceinline__ void xcd_decode(int MT, int& gtile, int& mtile) {
     const int xcd = blockIdx.x & 7;
     const int q = blockIdx.x >> 3;
     mtile = q % MT;
     gtile = (q / MT) * 8 + xcd;
-    (void)GT;
 }
 
 static inline int xcd_grid(int GT, int MT) {
     return ((GT + 7) & ~7) * MT;
 }
 
-// QKV projections for token group mtile + RoPE + KV append (the large-M
-// analog of k_qkv16; epilogue identical, tokens indexed globally).
+// -------------------------------------------------- k_qkv16 and k_ffn16
+// One template serves decode and large-M; MTK picks how a block finds its
+// (row tile, token tile):
+//   MTK = false  decode, T <= 64: block = row tile, one token panel of JT
+//                tiles (mtile = 0, jtw = JT); launched with MT = jtw_rt = 0.
+//   MTK = true   large-M, T > 64: xcd_decode over (row tiles) x (MT 64-token
+//                groups), panel stride jtw = jtw_rt = jt_width(T); JT = 4.
+// Everything after that is one body with the tokens indexed globally.
+// Written so that both halves compile to the code of the two separate
+// kernels each used to be — keep the expressions as they stand (a
+// `jt0 = mtile * JT` temporary already costs the large-M ffn kernels 4
+// instructions and up to 4 VGPRs; see tools/kernel_isa_diff.py).
+
+// QKV projections on MFMA + fused input RMSNorm + RoPE + KV append.
+// GQA: wk/wv have Ekv = Hkv*D rows (< E); KV cache rows are Ekv wide.
+// Tile space is [0, E/16) for wq then [.., +Ekv/16) each for wk/wv.
 // RT row tiles per wave share the B panel (its load + norm-build cost).
-template <int WT, int JT = 4, int RT = 1>
-__global__ __launch_bounds__(BLOCK) void k_qkv16_mt(
+template <int WT, int JT, int RT = 1, bool MTK = false>
+__global__ __launch_bounds__(BLOCK) void k_qkv16(
     WMat2 wq, WMat2 wk, WMat2 wv, const unsigned short* __restrict__ xprep,
     const unsigned short* __restrict__ normprep,
     const float* __restrict__ ss_in, float eps, float* __restrict__ q_buf,
     __half* __restrict__ k_cache, __half* __restrict__ v_cache,
     const int* __restrict__ pos, const int* __restrict__ seq,
     const float* __restrict__ inv_freq, int E, int Ekv, int D, int n_ctx,
-    int T, int MT, int jtw) {
-    int gtile, mtile;
+    int T, int MT, int jtw_rt) {
+    int gtile, mtile, jtw;
     const int tq = (E >> 4) / RT;
     const int tk = (Ekv >> 4) / RT;
-    const int GT = tq + 2 * tk;
-    xcd_decode(GT, MT, gtile, mtile);
-    if (gtile >= GT) return;
-    const int mat = (gtile < tq) ? 0 : (gtile < tq + tk) ? 1 : 2;
-    const int tile = gtile - ((mat == 0) ? 0 : (mat == 1) ? tq : tq + tk);
+    if (MTK) {
+        const int GT = tq + 2 * tk;
+        xcd_decode(MT, gtile, mtile);
+        if (gtile >= GT) return;
+        jtw = jtw_rt;
+    } else {
+        gtile = blockIdx.x;
+        mtile = 0;
+        jtw = JT;
+    }
+    // the decode half compares the block index unsigned, as blockIdx.x is
+    using TileIdx = typename std::conditional<MTK, int, unsigned>::type;
+    const TileIdx gt = gtile;
+    const int mat = (gt < tq) ? 0 : (gt < tq + tk) ? 1 : 2;
+    const int tile = gt - ((mat == 0) ? 0 : (mat == 1) ? tq : tq + tk);
     const WMat2& w = (mat == 0) ? wq : (mat == 1) ? wk : wv;
     const int lane = threadIdx.x & (WAVE - 1);
     const int j = lane & 15;
@@ -1002,7 +914,7 @@ __global__ __launch_bounds__(BLOCK) void k_qkv16_mt(
         const int j2 = (mtile * JT + jt) * 16 + j;
         if (j2 >= T) continue;
         const int p = pos[j2];
-        if (mat == 2) {
+        if (mat == 2) {  // V rows: straight f16 cache append
             __half* dst =
                 v_cache + ((size_t)seq[j2] * n_ctx + p) * Ekv + r0;
 #pragma unroll
@@ -1010,6 +922,7 @@ __global__ __launch_bounds__(BLOCK) void k_qkv16_mt(
                 dst[jj] = __float2half(acc[rt][0][jt][jj]);
             continue;
         }
+        // q/k: RoPE on in-lane pairs (rows r0+2q2, r0+2q2+1)
 #pragma unroll
         for (int q2 = 0; q2 < 2; ++q2) {
             const int e = r0 + 2 * q2;
@@ -1034,16 +947,19 @@ __global__ __launch_bounds__(BLOCK) void k_qkv16_mt(
     }
 }
 
-// Large-M GEMM with the fused residual + sumsq + xprep epilogue (wo / w2
-// consumers) or plain store. RES_SQ semantics match k_gemm16<GM_RES_SQ>.
-template <int WT, bool RES_SQ, int JT = 4, int RT = 1>
+// Large-M GEMM with the fused residual + sumsq + xprep epilogue of
+// k_gemm16<GM_RES_SQ> (wo / w2).
+// Not folded into k_gemm16 the way k_qkv16 / k_ffn16 are: giving the decode
+// modes this epilogue moved all 75 decode kernels (lm_head JT=4 RT=4: 2392
+// -> 2209 instructions, 220 -> 192 VGPRs; GM_RES_SQ JT=4: 1020 -> 829).
+template <int WT, int JT = 4, int RT = 1>
 __global__ __launch_bounds__(BLOCK) void k_gemm16_mt(
     WMat2 w, const unsigned short* __restrict__ bprep,
     float* __restrict__ y, unsigned short* __restrict__ xprep_out,
     float* __restrict__ ss_out, int T, int MT, int jtw) {
     int gtile, mtile;
     const int GT = (w.rows >> 4) / RT;
-    xcd_decode(GT, MT, gtile, mtile);
+    xcd_decode(MT, gtile, mtile);
     if (gtile >= GT) return;
     const int lane = threadIdx.x & (WAVE - 1);
     const int j = lane & 15;
@@ -1068,14 +984,12 @@ __global__ __launch_bounds__(BLOCK) void k_gemm16_mt(
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
             float v = acc[rt][0][jt][jj];
-            if (RES_SQ) {
-                v += y[(size_t)j2 * w.rows + r0 + jj];
-                sq += v * v;
-            }
+            v += y[(size_t)j2 * w.rows + r0 + jj];
+            sq += v * v;
             y[(size_t)j2 * w.rows + r0 + jj] = v;
             acc[rt][0][jt][jj] = v;
         }
-        if (RES_SQ && xprep_out != nullptr) {
+        if (xprep_out != nullptr) {
             uint2 o;
             o.x = pack_f16(acc[rt][0][jt][0], acc[rt][0][jt][1]);
             o.y = pack_f16(acc[rt][0][jt][2], acc[rt][0][jt][3]);
@@ -1084,7 +998,7 @@ __global__ __launch_bounds__(BLOCK) void k_gemm16_mt(
                 (((size_t)(r0 >> 3) * jtw + mtile * JT + jt) * 16 + j) * 8 +
                 (r0 & 7)) = o;
         }
-        if (RES_SQ && ss_out != nullptr) {
+        if (ss_out != nullptr) {
             float s2 = sq;
             s2 += __shfl_xor(s2, 16);
             s2 += __shfl_xor(s2, 32);
@@ -1094,17 +1008,25 @@ __global__ __launch_bounds__(BLOCK) void k_gemm16_mt(
     }
 }
 
-// Large-M w1/w3 + fused RMSNorm + SwiGLU -> gprep (analog of k_ffn16).
-template <int WT, int JT = 4, int RT = 1>
-__global__ __launch_bounds__(BLOCK) void k_ffn16_mt(
+// w1 + w3 against the same B panel + fused input RMSNorm + SwiGLU; emits
+// the gate product straight into gprep (f16 B-layout over F).
+template <int WT, int JT, int RT = 1, bool MTK = false>
+__global__ __launch_bounds__(BLOCK) void k_ffn16(
     WMat2 w1, WMat2 w3, const unsigned short* __restrict__ xprep,
     const unsigned short* __restrict__ normprep,
     const float* __restrict__ ss_in, float eps,
-    unsigned short* __restrict__ gprep, int T, int MT, int jtw) {
-    int gtile, mtile;
-    const int GT = (w1.rows >> 4) / RT;
-    xcd_decode(GT, MT, gtile, mtile);
-    if (gtile >= GT) return;
+    unsigned short* __restrict__ gprep, int T, int MT, int jtw_rt) {
+    int gtile, mtile, jtw;
+    if (MTK) {
+        const int GT = (w1.rows >> 4) / RT;
+        xcd_decode(MT, gtile, mtile);
+        if (gtile >= GT) return;
+        jtw = jtw_rt;
+    } else {
+        gtile = blockIdx.x;
+        mtile = 0;
+        jtw = JT;
+    }
     const int lane = threadIdx.x & (WAVE - 1);
     const int j = lane & 15;
     float acc[RT][2][JT][4];
@@ -1221,6 +1143,14 @@ void launch_prep_x(hipStream_t s, const float* x, unsigned short* xprep,
         }                                        \
     }
 
+// RT=2 (two row tiles per wave share one B panel: half the panel re-reads
+// and norm-build VALU per MFMA) is taken when the tile count is even and
+// the halved grid still fills the chip. MT = 64-token groups per row tile
+// (1 in decode).
+static inline bool rt2_fills(int tiles, int MT) {
+    return tiles % 2 == 0 && (tiles / 2) * MT >= 512;
+}
+
 int qkv16_ks(int E, int Ekv) {
     const int tiles3 = (E + 2 * Ekv) >> 4;
     int ks = 1;
@@ -1326,21 +1256,22 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
         }
         return 1;
     }
-    if (rt2_ok && tiles3 / 2 >= 512) {
+    if (rt2_ok && rt2_fills(tiles3, 1)) {
         // big models: RT=2 fused — halves the B-panel re-read while the
         // halved grid still fills the chip
         const dim3 grid(tiles3 / 2);
         DISPATCH_WT2(wq.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
             (k_qkv16<WTc, JTc, 2>), grid, dim3(BLOCK), 0, s, wq, wk, wv,
             xprep, normprep, ss_in, eps, q_buf, k_cache_layer,
-            v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T)));
+            v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T, 0,
+            0)));
         return 0;
     }
     const dim3 grid(tiles3);
     DISPATCH_WT2(wq.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
         (k_qkv16<WTc, JTc>), grid, dim3(BLOCK), 0, s, wq, wk, wv, xprep,
         normprep, ss_in, eps, q_buf, k_cache_layer, v_cache_layer, pos, seq,
-        inv_freq, E, Ekv, D, n_ctx, T)));
+        inv_freq, E, Ekv, D, n_ctx, T, 0, 0)));
     return 0;
 }
 
@@ -1349,18 +1280,18 @@ void launch_ffn16(hipStream_t s, const WMat2& w1, const WMat2& w3,
                   const unsigned short* normprep, const float* ss_in,
                   float eps, unsigned short* gprep, int T) {
     const int tilesF = w1.rows / 16;
-    if ((tilesF % 2) == 0 && tilesF / 2 >= 512) {
+    if (rt2_fills(tilesF, 1)) {
         const dim3 grid(tilesF / 2);
         DISPATCH_WT2(w1.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
             (k_ffn16<WTc, JTc, 2>), grid, dim3(BLOCK), 0, s, w1, w3, xprep,
-            normprep, ss_in, eps, gprep, T)));
+            normprep, ss_in, eps, gprep, T, 0, 0)));
         return;
     }
 
     const dim3 grid(tilesF);
     DISPATCH_WT2(w1.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
         (k_ffn16<WTc, JTc>), grid, dim3(BLOCK), 0, s, w1, w3, xprep,
-        normprep, ss_in, eps, gprep, T)));
+        normprep, ss_in, eps, gprep, T, 0, 0)));
 }
 
 void launch_qkv16_mt(hipStream_t s, const WMat2& wq, const WMat2& wk,
@@ -1376,10 +1307,10 @@ void launch_qkv16_mt(hipStream_t s, const WMat2& wq, const WMat2& wk,
     const bool rt2_ok = ((E >> 4) % 2 == 0) && ((Ekv >> 4) % 2 == 0);
     // RT=2 halves the B-panel reads + norm-build VALU per MFMA as long
     // as the halved grid still fills the chip
-    if (rt2_ok && (tiles3 / 2) * MT >= 512) {
+    if (rt2_ok && rt2_fills(tiles3, MT)) {
         const dim3 grid(xcd_grid(tiles3 / 2, MT));
         DISPATCH_WT2(wq.wtype, hipLaunchKernelGGL(
-            (k_qkv16_mt<WTc, 4, 2>), grid, dim3(BLOCK), 0, s, wq, wk, wv,
+            (k_qkv16<WTc, 4, 2, true>), grid, dim3(BLOCK), 0, s, wq, wk, wv,
             xprep, normprep, ss_in, eps, q_buf, k_cache_layer,
             v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T, MT,
             jtw));
@@ -1387,41 +1318,28 @@ void launch_qkv16_mt(hipStream_t s, const WMat2& wq, const WMat2& wk,
     }
     const dim3 grid(xcd_grid(tiles3, MT));
     DISPATCH_WT2(wq.wtype, hipLaunchKernelGGL(
-        (k_qkv16_mt<WTc>), grid, dim3(BLOCK), 0, s, wq, wk, wv, xprep,
+        (k_qkv16<WTc, 4, 1, true>), grid, dim3(BLOCK), 0, s, wq, wk, wv, xprep,
         normprep, ss_in, eps, q_buf, k_cache_layer, v_cache_layer, pos,
         seq, inv_freq, E, Ekv, D, n_ctx, T, MT, jtw));
 }
 
 void launch_gemm16_mt(hipStream_t s, const WMat2& w,
                       const unsigned short* bprep, float* y,
-                      unsigned short* xprep_out, float* ss_out, int T,
-                      int res_sq) {
+                      unsigned short* xprep_out, float* ss_out, int T) {
     const int MT = (T + 63) >> 6;
     const int jtw = jt_width(T);
     const int R = w.rows >> 4;
-    if (R % 2 == 0 && (R / 2) * MT >= 512) {
+    if (rt2_fills(R, MT)) {
         const dim3 grid(xcd_grid(R / 2, MT));
-        if (res_sq) {
-            DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
-                (k_gemm16_mt<WTc, true, 4, 2>), grid, dim3(BLOCK), 0, s, w,
-                bprep, y, xprep_out, ss_out, T, MT, jtw));
-        } else {
-            DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
-                (k_gemm16_mt<WTc, false, 4, 2>), grid, dim3(BLOCK), 0, s,
-                w, bprep, y, xprep_out, ss_out, T, MT, jtw));
-        }
+        DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
+            (k_gemm16_mt<WTc, 4, 2>), grid, dim3(BLOCK), 0, s, w, bprep, y,
+            xprep_out, ss_out, T, MT, jtw));
         return;
     }
     const dim3 grid(xcd_grid(R, MT));
-    if (res_sq) {
-        DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
-            (k_gemm16_mt<WTc, true>), grid, dim3(BLOCK), 0, s, w, bprep, y,
-            xprep_out, ss_out, T, MT, jtw));
-    } else {
-        DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
-            (k_gemm16_mt<WTc, false>), grid, dim3(BLOCK), 0, s, w, bprep, y,
-            xprep_out, ss_out, T, MT, jtw));
-    }
+    DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
+        (k_gemm16_mt<WTc>), grid, dim3(BLOCK), 0, s, w, bprep, y, xprep_out,
+        ss_out, T, MT, jtw));
 }
 
 void launch_ffn16_mt(hipStream_t s, const WMat2& w1, const WMat2& w3,
@@ -1431,15 +1349,15 @@ void launch_ffn16_mt(hipStream_t s, const WMat2& w1, const WMat2& w3,
     const int MT = (T + 63) >> 6;
     const int jtw = jt_width(T);
     const int R = w1.rows >> 4;
-    if (R % 2 == 0 && (R / 2) * MT >= 512) {
+    if (rt2_fills(R, MT)) {
         const dim3 grid(xcd_grid(R / 2, MT));
         DISPATCH_WT2(w1.wtype, hipLaunchKernelGGL(
-            (k_ffn16_mt<WTc, 4, 2>), grid, dim3(BLOCK), 0, s, w1, w3,
+            (k_ffn16<WTc, 4, 2, true>), grid, dim3(BLOCK), 0, s, w1, w3,
             xprep, normprep, ss_in, eps, gprep, T, MT, jtw));
         return;
     }
     const dim3 grid(xcd_grid(R, MT));
     DISPATCH_WT2(w1.wtype, hipLaunchKernelGGL(
-        (k_ffn16_mt<WTc>), grid, dim3(BLOCK), 0, s, w1, w3, xprep, normprep,
+        (k_ffn16<WTc, 4, 1, true>), grid, dim3(BLOCK), 0, s, w1, w3, xprep, normprep,
         ss_in, eps, gprep, T, MT, jtw));
 }

@@ -550,7 +550,7 @@ def check_kv_rows(name, k_got, v_got, k_ref, v_ref, pos):
 
 KV_POS = [0, 1, 511, 1607, 1609, 2047, 3000, 4095]
 KV_PRODUCERS = ["k_qkv_finish", "k_attention_fused", "k_qkv16_unsplit",
-                "k_qkv16_mt", "legacy_f32"]
+                "k_qkv16_large_m", "legacy_f32"]
 
 
 def kv_case(producer):
@@ -572,8 +572,8 @@ def kv_case(producer):
         "k_qkv16_unsplit": (LlamaPreset("kv_unsplit", 256, 128, 32, 8, 1,
                                         n_head_kv=1),
                             ggml.FTYPE_MOSTLY_Q4_0, False, 8),
-        # T > 64: the large-M path
-        "k_qkv16_mt": ("small", ggml.FTYPE_MOSTLY_Q4_0, False, 100),
+        # T > 64: k_qkv16<…, true> (large-M)
+        "k_qkv16_large_m": ("small", ggml.FTYPE_MOSTLY_Q4_0, False, 100),
         # f32 weights: launch_qkv_rope_append
         "legacy_f32": ("tiny", ggml.FTYPE_ALL_F32, False, 8),
     }[producer]

@@ -442,8 +442,8 @@ def test_slice_chain_matches_monolith_on_gpu():
 
 
 def test_native_prefill_path_matches_cpu():
-    """T > 64 takes the native large-M prefill path (k_qkv16_mt /
-    k_gemm16_mt / k_ffn16_mt — XCD-grouped token tiles, q4 read
+    """T > 64 takes the native large-M prefill path (k_qkv16<…, true> /
+    k_gemm16_mt / k_ffn16<…, true> — XCD-grouped token tiles, q4 read
     directly, the layer loop sequenced in C++) — must match the fp32
     CPU reference, and the kernel decode path must attend seamlessly
     over the KV rows it wrote."""
@@ -466,6 +466,27 @@ def test_native_prefill_path_matches_cpu():
                          decode=True).cpu()
     y2_cpu = cpu.forward(xd.clone(), pd, sd)
     _assert_close(y2_gpu, y2_cpu, label="decode after native prefill")
+
+
+def test_native_prefill_rt2_matches_cpu():
+    """The large-M launchers take RT=2 (two row tiles per wave) when the
+    tile count is even and (tiles / 2) * MT >= 512, MT = ceil(T / 64).
+    small has 96 qkv, 88 ffn and 32 wo/w2 row tiles; at T = 768, MT = 12:
+    qkv 48 * 12 = 576 and ffn 44 * 12 = 528 run k_qkv16<…, 2, true> and
+    k_ffn16<…, 2, true>, wo/w2 (16 * 12 = 192) stay RT=1. (T = 704 would
+    leave ffn at 484.) Must match the fp32 CPU reference."""
+    f, hip, cpu = _engines(preset="small", n_ctx=1024, max_batch=1)
+    hp = f.hparams
+    assert hip._mfma_path()
+    assert (hp.n_embd, hp.n_ff) == (512, 1408)  # the tile counts above
+    torch.manual_seed(14)
+    T = 768
+    x = torch.randn(T, hp.n_embd) * 0.5
+    pos = torch.arange(T, dtype=torch.int32)
+    seq = torch.zeros(T, dtype=torch.int32)
+    y_gpu = hip.forward(x.cuda(), pos.cuda(), seq.cuda()).cpu()
+    y_cpu = cpu.forward(x.clone(), pos, seq)
+    _assert_close(y_gpu, y_cpu, label="native prefill RT=2")
 
 
 def test_native_prefill_mixed_stream_matches_cpu():
@@ -495,7 +516,7 @@ def test_native_prefill_mixed_stream_matches_cpu():
 @pytest.mark.parametrize("ftype", [ggml.FTYPE_MOSTLY_Q8_0,
                                    ggml.FTYPE_MOSTLY_F16])
 def test_native_prefill_other_wtypes(ftype):
-    """The byte-stream (W_Q8B) and f16 tile paths run the same _mt
+    """The byte-stream (W_Q8B) and f16 tile paths run the same large-M
     prefill kernels."""
     f, hip, cpu = _engines(preset="small", ftype=ftype, n_ctx=256,
                            max_batch=1)
@@ -535,7 +556,7 @@ def test_gqa_hip_engine_matches_cpu(preset):
                          decode=True).cpu()
     y2_cpu = cpu.forward(xd.clone(), pd, sd)
     _assert_close(y2_gpu, y2_cpu, label=f"{preset} gqa fused decode")
-    # native large-T prefill (_mt kernels + MFMA flash attention)
+    # native large-T prefill (large-M kernels + MFMA flash attention)
     T2 = 100
     x3 = torch.randn(T2, hp.n_embd) * 0.5
     p3 = torch.arange(T + 1, T + 1 + T2, dtype=torch.int32)
@@ -603,8 +624,8 @@ def test_kquant_hip_engine_matches_cpu(ftype):
 
 
 def test_wide_decode_matches_tiled():
-    """decode with T > 64 (the wide batched-decode path through the _mt
-    kernels) must match the same step run as two <=64-token decode
+    """decode with T > 64 (the wide batched-decode path through the
+    large-M kernels) must match the same step run as two <=64-token decode
     calls on identical weights."""
     f = synthetic.build_model("small", ftype=ggml.FTYPE_MOSTLY_Q4_0,
                               seed=5)

@@ -4,7 +4,8 @@ twin's, row by row, built from the same model bytes. Layer 0 depends only
 on the input, so nothing else is in the comparison.
 
 One case per producer (attention_reference.kv_case): k_qkv_finish,
-k_attention<true>, k_qkv16 (unsplit), k_qkv16_mt and the legacy f32
+k_attention<true>, k_qkv16 (unsplit), k_qkv16<…, true> (large-M) and the
+legacy f32
 launch_qkv_rope_append. Every case writes rows at pos 0, 1, 511, 1607,
 1609, 2047, 3000 and 4095 - on both sides of the 512 pi (about 1608 rad)
 input domain older ISA manuals give for the hardware sin/cos, where pair 0
@@ -17,7 +18,7 @@ implementations, the multiply by 1/2pi adds about as much again). A lost
 rotation is an O(|k|) error; tests/test_attention_reference.py shows these
 assertions reject it at every deep position.
 
-Worst error / bound measured on an MI355X: K rows 44 % (k_qkv16_mt),
+Worst error / bound measured on an MI355X: K rows 52 % (k_qkv16<…, true>),
 V rows 73 % (k_attention<true>); no producer loses the rotation above
 pos 1608.
 """

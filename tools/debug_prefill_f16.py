@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Isolate the f16 _mt prefill divergence: run the same T-token prefill
-through (a) the 64-token tile path (known good) and (b) the _mt path,
+"""Isolate the f16 large-M prefill divergence: run the same T-token prefill
+through (a) the 64-token tile path (known good) and (b) the large-M path
+(k_qkv16<…, true> / k_gemm16_mt / k_ffn16<…, true>),
 compare the residual stream AND the KV caches layer by layer."""
 import os
 import sys
