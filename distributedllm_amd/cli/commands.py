@@ -574,9 +574,9 @@ def _local_perplexity(model_path: str, text: str) -> float:
     pos = torch.arange(len(tokens) - 1, dtype=torch.int32, device=dev)
     seq = torch.zeros(len(tokens) - 1, dtype=torch.int32, device=dev)
     y = eng.forward(eng.embed(ids), pos, seq)
-    lg = eng.logits(y, all_logits=True)
-    logp = torch.log_softmax(lg.float().cpu(), dim=-1).numpy()
-    nll = [-logp[i, tokens[i + 1]] for i in range(len(tokens) - 1)]
+    # scored on the engine: no [T, V] logits, only T floats come back
+    lp, _, _ = eng.score(y, tokens[1:])
+    nll = -lp.float().cpu().numpy()
     return float(np.exp(np.mean(nll)))
 
 

@@ -177,3 +177,32 @@ def logprobs_reference(logits_row, token_id, top_n=0):
         top_lp = x[top_ids] - lse
         lp = float(x[token_id] - lse)
     return lp, top_ids, top_lp
+
+
+def score_reference(logits_rows, targets):
+    """Prompt scoring in float64: row t of `logits_rows` [T, V] scored
+    against `targets[t]` - (lp [T], top_id [T], top_lp [T]).
+
+    `lp[t]` is the log-softmax value of the target under the raw logits,
+    `top_id[t]` the row's arg-max (a tie resolves to the smaller index) and
+    `top_lp[t]` its log-probability: `logprobs_reference(row, target, 1)`
+    row by row. A target outside [0, V) means "no target for this row":
+    `lp[t]` is NaN, the top entry is still reported. These are the
+    semantics the engines' `score()` is checked against."""
+    x = np.asarray(logits_rows, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("score_reference: logits_rows must be [T, V]")
+    tg = np.asarray(targets, dtype=np.int64).reshape(-1)
+    n, size = x.shape
+    if tg.shape[0] != n:
+        raise ValueError("score_reference: one target per row")
+    lp = np.full(n, np.nan)
+    top_id = np.empty(n, dtype=np.int64)
+    top_lp = np.empty(n)
+    for t in range(n):
+        ok = 0 <= tg[t] < size
+        v, ids, lps = logprobs_reference(x[t], tg[t] if ok else 0, 1)
+        if ok:
+            lp[t] = v
+        top_id[t], top_lp[t] = ids[0], lps[0]
+    return lp, top_id, top_lp

@@ -317,6 +317,53 @@ class HIPSliceEngine:
         return self._eng.logprobs(lg, rows_dev, ids, top_n,
                                   int(rows.max()))
 
+    # ---- prompt scoring (mfma_gemm.hip k_lmhead_score + logprobs.hip
+    # k_score_finish) ----
+
+    def score(self, x: torch.Tensor, targets):
+        """Score activation rows against their next tokens on the current
+        stream: the log-probability of targets[t] under final norm +
+        lm_head of x[t], and that row's arg-max, without forming [T, V]
+        logits. `targets` is a host sequence or a device i32 tensor [T]; a
+        target outside the vocabulary means "no target" (lp = NaN, the top
+        entry is still reported). Returns device tensors (lp [T] f32,
+        top_id [T] i32, top_lp [T] f32) - semantics of
+        engine.sampler.score_reference. Inputs longer than max_prefill are
+        tiled. A legacy f32 lm_head composes logits() + logprobs()
+        instead."""
+        if x.dim() != 2 or x.shape[0] < 1:
+            raise ValueError("score: x must be [T, E] with T >= 1")
+        T = x.shape[0]
+        if isinstance(targets, torch.Tensor):
+            tg = targets.to(self.device, torch.int32).reshape(-1)
+        else:
+            tg = torch.from_numpy(np.asarray(
+                targets, dtype=np.int64).reshape(-1).astype(np.int32)).to(
+                self.device)
+        if tg.shape[0] != T:
+            raise ValueError("score: one target per row of x")
+        if self._eng.out_mfma:
+            cap = int(self._eng.max_prefill)
+            parts = [self._eng.score(x[t0:t0 + cap].contiguous(),
+                                     tg[t0:t0 + cap].contiguous())
+                     for t0 in range(0, T, cap)]
+        else:
+            cap = int(self._eng.max_tokens)
+            V = self.hp.n_vocab
+            parts = []
+            for t0 in range(0, T, cap):
+                lg = self._eng.logits(x[t0:t0 + cap].contiguous(), True)
+                t = tg[t0:t0 + cap]
+                ok = (t >= 0) & (t < V)
+                lp, ti, tl = self.logprobs(
+                    lg, range(lg.shape[0]),
+                    torch.where(ok, t, torch.zeros_like(t)), 1)
+                parts.append((torch.where(ok, lp, torch.full_like(
+                    lp, float("nan"))), ti[:, 0], tl[:, 0]))
+        if len(parts) == 1:
+            return parts[0]
+        return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
+
 
 class TorchSliceEngine:
     """CPU twin with the identical stateless interface (fp32 torch math).
@@ -461,6 +508,32 @@ class TorchSliceEngine:
                 lg64[int(rows[r])], int(ids[r]), top_n)
         return (torch.from_numpy(lp), torch.from_numpy(top_ids),
                 torch.from_numpy(top_lp))
+
+    def score(self, x: torch.Tensor, targets):
+        """Twin of HIPSliceEngine.score: f32 logits, f32 `log_softmax` and
+        a gather (the arithmetic of the perplexity command); the arg-max
+        takes the smaller index on a tie."""
+        if x.dim() != 2 or x.shape[0] < 1:
+            raise ValueError("score: x must be [T, E] with T >= 1")
+        if isinstance(targets, torch.Tensor):
+            tg = targets.detach().cpu().numpy()
+        else:
+            tg = np.asarray(targets)
+        tg = tg.astype(np.int64).reshape(-1)
+        if tg.shape[0] != x.shape[0]:
+            raise ValueError("score: one target per row of x")
+        lg = self.logits(x, all_logits=True)
+        logp = torch.log_softmax(lg.float().cpu(), dim=-1).numpy()
+        rows = np.arange(len(tg))
+        ok = (tg >= 0) & (tg < logp.shape[1])
+        lp = np.full(len(tg), np.nan, dtype=np.float32)
+        lp[ok] = logp[rows[ok], tg[ok]]
+        # numpy's argmax returns the first (smallest) index of the maximum
+        top_id = lg.float().cpu().numpy().argmax(axis=1)
+        top_lp = logp[rows, top_id]
+        return (torch.from_numpy(lp),
+                torch.from_numpy(top_id.astype(np.int32)),
+                torch.from_numpy(top_lp.astype(np.float32)))
 
 
 def engine_for_slice(f: ggml.GGMLFile, n_ctx: int, max_batch: int,

@@ -20,7 +20,8 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 SOURCES = [CSRC / "mfma_gemm.hip", CSRC / "attention.hip",
            CSRC / "scalar_ops.hip", CSRC / "sampling.hip",
            CSRC / "logprobs.hip", CSRC / "engine_ext.cpp"]
-HEADERS = [CSRC / "kernels.h", CSRC / "device_common.h"]
+HEADERS = [CSRC / "kernels.h", CSRC / "device_common.h",
+           CSRC / "logprobs_key.h"]
 
 
 def _torch_paths():

@@ -589,6 +589,63 @@ class SliceEngine {
         return {lp, top_ids, top_lp};
     }
 
+    // Prompt scoring: log-probability of targets[t] under final norm +
+    // lm_head of row t, and the row's arg-max, with no [T, V] logits (the
+    // kernels.h "prompt scoring" sequence, all on the current stream). x is
+    // [T, E] f32 with T <= max_prefill, targets a device i32 [T]; a target
+    // outside [0, V) marks "no target": lp NaN, top still written. Returns
+    // (lp [T] f32, top_id [T] i32, top_lp [T] f32).
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> score(
+        torch::Tensor x, torch::Tensor targets) {
+        TORCH_CHECK(has_extra_, "extra layers not loaded");
+        TORCH_CHECK(out_mfma_, "score: the lm_head is not on the MFMA path");
+        check_f32(x, "x");
+        check_i32(targets, "targets");
+        TORCH_CHECK(x.dim() == 2 && x.size(1) == E_, "x must be [T, E]");
+        const int T = (int)x.size(0);
+        TORCH_CHECK(T >= 1 && T <= maxP_, "score handles at most ", maxP_,
+                    " rows per call; tile larger inputs host-side");
+        TORCH_CHECK(targets.dim() == 1 && targets.size(0) == T,
+                    "score: targets must be [T]");
+        auto dev = torch::TensorOptions().device(torch::kCUDA);
+        auto f32 = dev.dtype(torch::kFloat32);
+        if (!score_key_.defined()) {
+            // first use: engines that never score allocate nothing. The
+            // partial count is largest where RT is smallest, at T = 1.
+            const int64_t pmax = V_ / (16 * lmhead_score_rt(V_, 1));
+            const int64_t ssn = ((int64_t)maxP_ + 63) & ~(int64_t)63;
+            ss_score_ = torch::zeros({ssn}, f32);
+            score_key_ = torch::zeros({(int64_t)maxP_ * pmax},
+                                      dev.dtype(torch::kInt64));
+            score_sum_ = torch::zeros({(int64_t)maxP_ * pmax}, f32);
+            score_tgt_ = torch::zeros({(int64_t)maxP_}, f32);
+        }
+        const int P = V_ / (16 * lmhead_score_rt(V_, T));
+        TORCH_CHECK((int64_t)T * P <= score_key_.numel(),
+                    "score: partials buffer too small");
+        auto lp = torch::empty({T}, f32);
+        auto top_lp = torch::empty({T}, f32);
+        auto top_id = torch::empty({T}, dev.dtype(torch::kInt32));
+        hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+        float* ss = ss_score_.data_ptr<float>();
+        auto* pkey =
+            reinterpret_cast<unsigned long long*>(score_key_.data_ptr());
+        (void)hipMemsetAsync(ss, 0, sizeof(float) * ss_score_.numel(), s);
+        launch_prep_x_score(s, x.data_ptr<float>(), u16p(xprep_), ss, E_, T);
+        launch_lmhead_score(s, mout_.w, u16p(xprep_), u16p(final_normprep_),
+                            ss, eps_, targets.data_ptr<int>(), pkey,
+                            score_sum_.data_ptr<float>(),
+                            score_tgt_.data_ptr<float>(), T);
+        launch_score_finish(s, pkey, score_sum_.data_ptr<float>(),
+                            score_tgt_.data_ptr<float>(),
+                            targets.data_ptr<int>(), lp.data_ptr<float>(),
+                            top_id.data_ptr<int>(), top_lp.data_ptr<float>(),
+                            T, P, V_);
+        return {lp, top_id, top_lp};
+    }
+
+    bool out_mfma() const { return out_mfma_; }
+
     int64_t max_tokens() const { return kMaxTokens; }
     int64_t max_prefill() const { return maxP_; }
     int64_t n_ctx() const { return ctx_; }
@@ -636,6 +693,8 @@ class SliceEngine {
     torch::Tensor xn_, qb_, ab_, ffb_;
     torch::Tensor xprep_, aprep_, gprep_, ss_attn_, ss_ffn_, ss_tmp_;
     torch::Tensor argmax_keys_, slab_;
+    // prompt scoring, allocated by the first score() call
+    torch::Tensor ss_score_, score_key_, score_sum_, score_tgt_;
     bool has_extra_ = false;
     bool out_mfma_ = false;
     DevMat tok_, out_;
@@ -833,6 +892,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("qkv16_ks", [](int64_t E, int64_t Ekv) {
         return (int64_t)qkv16_ks((int)E, (int)Ekv);
     }, py::arg("E"), py::arg("Ekv"));
+    m.def("lmhead_score_rt", [](int64_t V, int64_t T) {
+        return (int64_t)lmhead_score_rt((int)V, (int)T);
+    }, py::arg("V"), py::arg("T"));
     m.def("jt_width", [](int64_t T) { return (int64_t)jt_width((int)T); },
           py::arg("T"));
     m.doc() = "MI355X-native layer-slice inference engine (CDNA4 HIP kernels)";
@@ -857,6 +919,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("logprobs", &SliceEngine::logprobs, py::arg("logits"),
              py::arg("rows"), py::arg("ids"), py::arg("top_n"),
              py::arg("row_max"))
+        .def("score", &SliceEngine::score, py::arg("x"), py::arg("targets"))
+        .def_property_readonly("out_mfma", &SliceEngine::out_mfma)
         .def_property_readonly("max_tokens", &SliceEngine::max_tokens)
         .def_property_readonly("max_prefill", &SliceEngine::max_prefill)
         .def_property_readonly("n_ctx", &SliceEngine::n_ctx)

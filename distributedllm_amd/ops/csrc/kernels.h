@@ -130,6 +130,36 @@ void launch_logprobs(hipStream_t s, const float* logits, const int* rows,
                      const int* ids, float* lp, int* top_ids, float* top_lp,
                      int R, int T, int V, int top_n);
 
+// ------------------------------------------------------- prompt scoring
+// Log-probability of targets[t] under the lm_head applied to row t of a
+// [T, E] activation block, plus the row's arg-max, without ever forming
+// [T, V] logits. Three launches on one stream:
+//   launch_prep_x_score  launch_prep_x at the scoring panel width (whole
+//                        4-tile groups at every T); ss zeroed upstream,
+//                        ss must hold T rounded up to 64 floats
+//   launch_lmhead_score  k_lmhead_score: fused final norm + lm_head with a
+//                        log-sum-exp epilogue -> P = V / (16 * RT) partials
+//                        per token, pkey/psum [T][P], and tgt_logit [T]
+//   launch_score_finish  k_score_finish: lp[t], top_id[t], top_lp[t]
+// A target outside [0, V) gives lp = NaN; top_id / top_lp are still
+// written. RT = lmhead_score_rt(V, T).
+int lmhead_score_rt(int V, int T);
+
+void launch_prep_x_score(hipStream_t s, const float* x,
+                         unsigned short* xprep, float* ss, int cols, int T);
+
+void launch_lmhead_score(hipStream_t s, const WMat2& w,
+                         const unsigned short* bprep,
+                         const unsigned short* normprep, const float* ss_in,
+                         float eps, const int* targets,
+                         unsigned long long* pkey, float* psum,
+                         float* tgt_logit, int T);
+
+void launch_score_finish(hipStream_t s, const unsigned long long* pkey,
+                         const float* psum, const float* tgt_logit,
+                         const int* targets, float* lp, int* top_id,
+                         float* top_lp, int T, int P, int V);
+
 // ---------------------------------------------------------- prefill path
 // Large-M (T > 64) layer launchers: one launch covers all T tokens with an
 // XCD-aware (row-tile x 64-token-group) grid. Side channels use the

@@ -32,6 +32,7 @@
 // wave partials from LDS in wave order. No atomics; identical inputs give
 // bit-identical lp and top_lp.
 #include "kernels.h"
+#include "logprobs_key.h"
 
 namespace {
 
@@ -44,14 +45,6 @@ struct LogprobsSmem {
     u64 wkey[LWAVES];
     float wsum[LWAVES];
 };
-
-__device__ __forceinline__ u64 logprobs_key(float v, int i) {
-    if (v == 0.0f) v = 0.0f;  // -0.0 -> +0.0
-    union { float f; uint32_t u; } c;
-    c.f = v;
-    const uint32_t o = (c.u & 0x80000000u) ? ~c.u : (c.u | 0x80000000u);
-    return ((u64)o << 32) | (uint32_t)(~i);
-}
 
 // the largest key of the row that is < below (0 if there is none)
 __device__ u64 logprobs_best(const float* __restrict__ lg, int V, u64 below,
@@ -121,7 +114,63 @@ __global__ __launch_bounds__(LBLOCK) void k_logprobs(
     }
 }
 
+// ------------------------------------------------------- k_score_finish
+// Second half of prompt scoring (first half: k_lmhead_score in
+// mfma_gemm.hip). Per token t the lm_head pass left P vocabulary-tile
+// partials: the tile's arg-max key pkey[t][p] and psum[t][p] = sum over
+// the tile of exp(v - tile max), plus the target's logit tgt_logit[t]
+// (written only when the target lies in [0, V)). One wave per token:
+//   M, top id  the largest key (value / index it was packed from)
+//   S          sum_p psum[p] * exp(m_p - M)
+//   lse = M + log S;  lp = tgt_logit - lse (NaN for a target outside the
+//   vocabulary), top_lp = M - lse.
+// Each lane takes partials p = lane, lane + 64, ... in index order and the
+// wave combines with the xor-butterfly of k_logprobs: fixed shape, no
+// atomics, bit-identical results for identical partials.
+__global__ __launch_bounds__(64) void k_score_finish(
+    const u64* __restrict__ pkey, const float* __restrict__ psum,
+    const float* __restrict__ tgt_logit, const int* __restrict__ targets,
+    float* __restrict__ lp, int* __restrict__ top_id,
+    float* __restrict__ top_lp, int P, int V) {
+    const int t = blockIdx.x;
+    const int lane = threadIdx.x;
+    const u64* kt = pkey + (size_t)t * P;
+    const float* st = psum + (size_t)t * P;
+    u64 best = 0;
+    for (int p = lane; p < P; p += 64) {
+        const u64 k = kt[p];
+        best = k > best ? k : best;
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const u64 o = __shfl_xor(best, d, 64);
+        best = o > best ? o : best;
+    }
+    const float M = logprobs_key_value(best);
+    float part = 0.0f;
+    for (int p = lane; p < P; p += 64) {
+        const float s = st[p];
+        // an all -inf tile has s == 0 and contributes nothing
+        if (s > 0.0f) part += s * expf(logprobs_key_value(kt[p]) - M);
+    }
+    for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d, 64);
+    if (lane != 0) return;
+    const float lse = M + logf(part);
+    const int tg = targets[t];
+    lp[t] = (tg >= 0 && tg < V) ? tgt_logit[t] - lse : NAN;
+    top_id[t] = logprobs_key_index(best);
+    top_lp[t] = M - lse;
+}
+
 }  // namespace
+
+void launch_score_finish(hipStream_t s, const unsigned long long* pkey,
+                         const float* psum, const float* tgt_logit,
+                         const int* targets, float* lp, int* top_id,
+                         float* top_lp, int T, int P, int V) {
+    if (T <= 0 || P <= 0) return;
+    hipLaunchKernelGGL(k_score_finish, dim3(T), dim3(64), 0, s, pkey, psum,
+                       tgt_logit, targets, lp, top_id, top_lp, P, V);
+}
 
 void launch_logprobs(hipStream_t s, const float* logits, const int* rows,
                      const int* ids, float* lp, int* top_ids, float* top_lp,

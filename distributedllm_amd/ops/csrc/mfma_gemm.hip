@@ -1,8 +1,10 @@
 // MFMA dequant-GEMM family of the slice engine (gfx950) — the production
 // path for every quantized / f16 layer, decode (T <= 64) and large-M
 // prefill / wide decode (T > 64: `k_qkv16<…, true>`, `k_ffn16<…, true>`,
-// `k_gemm16_mt`, behind the launch_*_mt launchers). Design notes with the
-// measurements that drove each choice: docs/kernels.md.
+// `k_gemm16_mt`, behind the launch_*_mt launchers), plus the lm_head of
+// prompt scoring at any T (`k_lmhead_score`: large-M grid, log-sum-exp
+// epilogue, no logits). Design notes with the measurements that drove
+// each choice: docs/kernels.md.
 //
 // Matrix cores do the FLOPs; the VALU only unpacks. One
 // `mfma_f32_16x16x32_f16` consumes one 32-weight K-block of a 16-row tile.
@@ -55,6 +57,7 @@
 
 #include "device_common.h"
 #include "kernels.h"
+#include "logprobs_key.h"
 
 // write-through 16 B store (sc0 sc1): the split-K slab publish leaves no
 // dirty lines in the writer XCD's L2, so the consumer kernel's reads are
@@ -1063,6 +1066,89 @@ __global__ __launch_bounds__(BLOCK) void k_ffn16(
     }
 }
 
+// ------------------------------------------------------- k_lmhead_score
+// Large-M lm_head for prompt scoring: k_gemm16_mt's grid, the fused final
+// RMSNorm of k_gemm16<GM_NORM_PLAIN>, and an epilogue that stores NO
+// logits. A block owns 16*RT vocabulary rows x 64 tokens; per token column
+// wave 0 reduces its rows (4 lanes x 4 jj x RT) to one log-sum-exp partial
+//   pkey[t][gtile] = largest logprobs_key (tile max and its arg-max, ties
+//                    to the smaller index),
+//   psum[t][gtile] = sum exp(v - tile max),
+// and the one lane that holds row targets[t] stores that logit to
+// tgt_logit[t] (one writer per token). k_score_finish (logprobs.hip) merges
+// the P = V / (16*RT) partials of a token. Fixed reduction shape, no
+// atomics: the result depends on the inputs alone.
+template <int WT, int RT>
+__global__ __launch_bounds__(BLOCK) void k_lmhead_score(
+    WMat2 w, const unsigned short* __restrict__ bprep,
+    const unsigned short* __restrict__ normprep,
+    const float* __restrict__ ss_in, float eps,
+    const int* __restrict__ targets, unsigned long long* __restrict__ pkey,
+    float* __restrict__ psum, float* __restrict__ tgt_logit, int T, int MT,
+    int jtw) {
+    constexpr int JT = 4;
+    int gtile, mtile;
+    const int GT = (w.rows >> 4) / RT;
+    xcd_decode(MT, gtile, mtile);
+    if (gtile >= GT) return;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int j = lane & 15;
+    float acc[RT][1][JT][4];
+    const WMat2* ws[1] = {&w};
+    const int nbt = w.cols >> 5;
+    const int nbk = (WT == W_F16) ? nbt : ((nbt + 3) & ~3);
+    wave_tile_kloop<WT, true, 1, JT, RT>(ws, gtile, bprep, normprep, ss_in,
+                                         eps, acc, 0, nbk, jtw, mtile * JT);
+    __shared__ float lds[3 * 64 * 4 * JT * RT];
+    combine_acc<RT * JT>(reinterpret_cast<float(*)[4]>(acc), lds);
+    if (threadIdx.x >= WAVE) return;
+    // first of this lane's rows in row tile 0 of the block
+    const int rbase = gtile * RT * 16 + (lane >> 4) * 4;
+#pragma unroll
+    for (int jt = 0; jt < JT; ++jt) {
+        const int j2 = (mtile * JT + jt) * 16 + j;
+        // every lane runs the reductions (dead columns hold finite
+        // garbage); only the stores are bounded by T
+        unsigned long long best = 0;
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                const unsigned long long k = logprobs_key(
+                    acc[rt][0][jt][jj], rbase + rt * 16 + jj);
+                best = k > best ? k : best;
+            }
+        {
+            unsigned long long o = __shfl_xor(best, 16);
+            best = o > best ? o : best;
+            o = __shfl_xor(best, 32);
+            best = o > best ? o : best;
+        }
+        const float m = logprobs_key_value(best);
+        float sum = 0.0f;
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+                sum += expf(acc[rt][0][jt][jj] - m);
+        sum += __shfl_xor(sum, 16);
+        sum += __shfl_xor(sum, 32);
+        if (!(m > -INFINITY)) sum = 0.0f;  // all -inf tile: no mass
+        if (j2 >= T) continue;
+        // target logit: rel = target row relative to this lane's first row
+        const int rel = targets[j2] - rbase;
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+                if (rel == rt * 16 + jj) tgt_logit[j2] = acc[rt][0][jt][jj];
+        if (lane < 16) {
+            pkey[(size_t)j2 * GT + gtile] = best;
+            psum[(size_t)j2 * GT + gtile] = sum;
+        }
+    }
+}
+
 // ============================================================== launchers
 
 // column-tile count for a token batch T (1, 2 or 4 tiles of 16)
@@ -1360,4 +1446,61 @@ void launch_ffn16_mt(hipStream_t s, const WMat2& w1, const WMat2& w3,
     DISPATCH_WT2(w1.wtype, hipLaunchKernelGGL(
         (k_ffn16<WTc, 4, 1, true>), grid, dim3(BLOCK), 0, s, w1, w3, xprep, normprep,
         ss_in, eps, gprep, T, MT, jtw));
+}
+
+// ------------------------------------------------------ prompt scoring
+// token-panel stride of the scoring path: whole 4-tile groups at EVERY T
+// (k_lmhead_score is JT=4 only, so unlike jt_width it never packs 1 or 2)
+static inline int score_jtw(int T) {
+    return (((T + 15) >> 4) + 3) & ~3;
+}
+
+void launch_prep_x_score(hipStream_t s, const float* x,
+                         unsigned short* xprep, float* ss, int cols,
+                         int T) {
+    const int want = (128 + T - 1) / max(T, 1);  // see launch_prep_x
+    const int chunks = max(1, min(want, (cols >> 3) / 64));
+    hipLaunchKernelGGL(k_prep_x, dim3(T, chunks), dim3(BLOCK), 0, s, x,
+                       xprep, ss, cols, score_jtw(T));
+}
+
+// Row tiles per wave of k_lmhead_score: the lm_head rule of launch_gemm16
+// (RT=4 from 448 blocks, RT=2 from 512) with the block count taken over
+// the MT token groups the way rt2_fills does for the other large-M kernels.
+int lmhead_score_rt(int V, int T) {
+    const int R = V >> 4;
+    const int MT = (T + 63) >> 6;
+    if (R % 4 == 0 && (R / 4) * MT >= 448) return 4;
+    if (rt2_fills(R, MT)) return 2;
+    return 1;
+}
+
+void launch_lmhead_score(hipStream_t s, const WMat2& w,
+                         const unsigned short* bprep,
+                         const unsigned short* normprep, const float* ss_in,
+                         float eps, const int* targets,
+                         unsigned long long* pkey, float* psum,
+                         float* tgt_logit, int T) {
+    const int MT = (T + 63) >> 6;
+    const int jtw = score_jtw(T);
+    const int R = w.rows >> 4;
+    switch (lmhead_score_rt(w.rows, T)) {
+        case 4:
+            DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
+                (k_lmhead_score<WTc, 4>), dim3(xcd_grid(R / 4, MT)),
+                dim3(BLOCK), 0, s, w, bprep, normprep, ss_in, eps, targets,
+                pkey, psum, tgt_logit, T, MT, jtw));
+            break;
+        case 2:
+            DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
+                (k_lmhead_score<WTc, 2>), dim3(xcd_grid(R / 2, MT)),
+                dim3(BLOCK), 0, s, w, bprep, normprep, ss_in, eps, targets,
+                pkey, psum, tgt_logit, T, MT, jtw));
+            break;
+        default:
+            DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
+                (k_lmhead_score<WTc, 1>), dim3(xcd_grid(R, MT)),
+                dim3(BLOCK), 0, s, w, bprep, normprep, ss_in, eps, targets,
+                pkey, psum, tgt_logit, T, MT, jtw));
+    }
 }

@@ -16,16 +16,23 @@ Endpoints:
              "repeat_penalty": float = 1.1, "seed": int | None,
              "top_k": int = 0, "top_p": float = 1.0,
              "stop": [str, ...] | None,  # end at first stop string
-             "logprobs": int | None}     # 0..8: per-token logprobs
+             "logprobs": int | None,     # 0..8: per-token logprobs
+             "echo": bool = false}       # also score the prompt tokens
       with "logprobs" set the response gains
       "logprobs": {"token_logprobs": [...], "top_logprobs": [[{"id",
       "token", "logprob"}, ...], ...]} (raw-logit log-softmax, independent
-      of the sampler settings; -inf serialises as null)
+      of the sampler settings; -inf serialises as null); with "echo"
+      (needs "logprobs"; "num_tokens": 0 then scores without generating)
+      that object gains "prompt_token_logprobs" / "prompt_top_logprobs",
+      one entry per prompt token, the first null
   POST /generate_stream   -> SSE, one data: line per token piece (plus
-      "logprob" / "top_logprobs" per event when "logprobs" is set)
+      "logprob" / "top_logprobs" per event when "logprobs" is set);
+      "echo" is not supported here (422)
   POST /v1/completions    -> OpenAI-compatible completions shape; integer
       "logprobs" fills choices[0].logprobs (tokens, token_logprobs,
-      top_logprobs, text_offset)
+      top_logprobs, text_offset); "echo": true puts the prompt in front
+      of the text and of those four lists (first token_logprobs entry
+      null), and accepts "max_tokens": 0
   GET  /metrics           -> lifetime counters incl. tokens_per_step
 """
 from __future__ import annotations
@@ -53,6 +60,7 @@ class GenerateRequest(BaseModel):
     #                                one; the stop text is not returned
     logprobs: Optional[int] = None  # 0..8: the chosen token's logprob plus
     #                                that many most likely alternatives
+    echo: bool = False             # with logprobs: score the prompt too
 
 
 def _json_lp(v):
@@ -131,13 +139,14 @@ class BatcherWorker:
     def submit_and_wait(self, prompt_ids, max_new,
                         sampler: Optional[Sampler],
                         timeout: float = 300.0,
-                        stop_check=None, logprobs: Optional[int] = None):
+                        stop_check=None, logprobs: Optional[int] = None,
+                        echo: bool = False):
         """stop_check(req) -> bool: called on every step wake; True
         cancels the request (used for stop-string termination — the
         caller trims the output afterwards)."""
         with self.cond:
             req = self.batcher.submit(prompt_ids, max_new, sampler=sampler,
-                                      logprobs=logprobs)
+                                      logprobs=logprobs, echo=echo)
             self.cond.notify_all()
             deadline = time.monotonic() + timeout
             seen = 0
@@ -185,7 +194,7 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
                     stats["tokens"] / max(up, 1e-9), 1)}
 
     def _submit(r: GenerateRequest):
-        if r.num_tokens < 1:
+        if r.num_tokens < 1 and not (r.echo and r.num_tokens == 0):
             raise HTTPException(422, "num_tokens must be >= 1")
         ids = tokenizer.encode(r.prompt, bos=True)
         sampler = None
@@ -196,6 +205,11 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
 
     @app.post("/generate")
     def generate(r: GenerateRequest):
+        return _generate(r)[0]
+
+    def _generate(r: GenerateRequest):
+        """(response body, request): /v1/completions needs the request's
+        prompt records next to the body /generate returns."""
         ids, sampler = _submit(r)
         stops = [s for s in (r.stop or []) if s]
         check = None
@@ -205,7 +219,7 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
         try:
             req = worker.submit_and_wait(ids, r.num_tokens, sampler,
                                          stop_check=check,
-                                         logprobs=r.logprobs)
+                                         logprobs=r.logprobs, echo=r.echo)
         except ValueError as e:        # oversized prompt+num_tokens, or
             #                            logprobs the batcher rejects
             raise HTTPException(422, str(e))
@@ -225,7 +239,14 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
                                    for v in req.out_logprobs[:n]],
                 "top_logprobs": [_top_entries(tokenizer, top)
                                  for top in req.out_top[:n]]}
-        return out
+            if r.echo:
+                out["logprobs"]["prompt_token_logprobs"] = [
+                    None if v is None else _json_lp(v)
+                    for v in req.prompt_logprobs]
+                out["logprobs"]["prompt_top_logprobs"] = [
+                    None if top is None else _top_entries(tokenizer, top)
+                    for top in req.prompt_top]
+        return out, req
 
     @app.post("/generate_stream")
     def generate_stream(r: GenerateRequest):
@@ -237,6 +258,8 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
 
         from fastapi.responses import StreamingResponse
 
+        if r.echo:
+            raise HTTPException(422, "echo is not supported when streaming")
         ids, sampler = _submit(r)
         stops = [s for s in (r.stop or []) if s]
         with worker.cond:
@@ -336,22 +359,38 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
             if isinstance(want_lp, bool) or not isinstance(want_lp, int):
                 raise HTTPException(400, "logprobs must be an integer")
             r.logprobs = want_lp
-        out = generate(r)
+        echo = body.get("echo", False)
+        if not isinstance(echo, bool):
+            raise HTTPException(422, "echo must be a boolean")
+        r.echo = echo
+        out, req = _generate(r)
+        text = out["text"]
+        toks = out["tokens"]
+        if echo:
+            # the prompt as the tokenizer renders it, so that text_offset
+            # indexes the returned text
+            text = tokenizer.decode(req.prompt) + text
+            toks = list(req.prompt) + toks
         lp = None
         if want_lp is not None:
             # OpenAI shape; text_offset indexes the returned text
-            pieces = [tokenizer.decode_token(t) for t in out["tokens"]]
+            pieces = [tokenizer.decode_token(t) for t in toks]
             offs, at = [], 0
-            for t in out["tokens"]:     # decode() drops BOS/EOS pieces
-                offs.append(min(at, len(out["text"])))
+            for t in toks:              # decode() drops BOS/EOS pieces
+                offs.append(min(at, len(text)))
                 at += len(tokenizer.decode([t]))
+            tlp = out["logprobs"]["token_logprobs"]
+            tops = out["logprobs"]["top_logprobs"]
+            if echo:
+                tlp = out["logprobs"]["prompt_token_logprobs"] + tlp
+                tops = out["logprobs"]["prompt_top_logprobs"] + tops
             lp = {"tokens": pieces,
-                  "token_logprobs": out["logprobs"]["token_logprobs"],
+                  "token_logprobs": tlp,
                   # ids that decode to one piece share a key: the most
                   # likely one keeps it
-                  "top_logprobs": [{e["token"]: e["logprob"]
-                                    for e in reversed(top)} for top in
-                                   out["logprobs"]["top_logprobs"]],
+                  "top_logprobs": [None if top is None else
+                                   {e["token"]: e["logprob"]
+                                    for e in reversed(top)} for top in tops],
                   "text_offset": offs}
         stats["v1_id"] = stats.get("v1_id", 0) + 1
         return {
@@ -359,7 +398,7 @@ def build_app(batcher, tokenizer, eos_id: Optional[int] = None):
             "object": "text_completion",
             "model": body.get("model", "distllm-mi355x"),
             "choices": [{
-                "text": out["text"],
+                "text": text,
                 "index": 0,
                 "logprobs": lp,
                 "finish_reason":

@@ -52,6 +52,13 @@ class Request:
     logprobs: Optional[int] = None
     out_logprobs: List[float] = field(default_factory=list)
     out_top: List[List[Tuple[int, float]]] = field(default_factory=list)
+    # echo: the same two records for the PROMPT tokens, filled as the
+    # prefill passes. Index-aligned with `prompt`; entry 0 is None (the
+    # first token has no context to be predicted from)
+    echo: bool = False
+    prompt_logprobs: List[Optional[float]] = field(default_factory=list)
+    prompt_top: List[Optional[List[Tuple[int, float]]]] = field(
+        default_factory=list)
 
 
 class ContinuousBatcher:
@@ -145,7 +152,8 @@ class ContinuousBatcher:
     def submit(self, prompt_ids: Sequence[int], max_new: int,
                sampler: Optional[Sampler] = None,
                eos_id: Optional[int] = None,
-               logprobs: Optional[int] = None) -> Request:
+               logprobs: Optional[int] = None,
+               echo: bool = False) -> Request:
         """Raises ValueError (before any slot is taken) on an invalid or
         oversized request — the caller can reject it (HTTP 422) without
         the decode loop ever seeing it.
@@ -154,7 +162,16 @@ class ContinuousBatcher:
         log-probability under the raw logits (`Request.out_logprobs`) and
         the n most likely tokens with theirs (`Request.out_top`) — the
         semantics of `engine.sampler.logprobs_reference`, independent of
-        the sampler settings. Needs an engine with `logprobs()`."""
+        the sampler settings. Needs an engine with `logprobs()`.
+
+        echo: also record the log-probability of every PROMPT token given
+        the tokens before it (`Request.prompt_logprobs`, entry 0 None) and
+        the `logprobs` most likely tokens at each prompt position
+        (`Request.prompt_top`) - `engine.sampler.score_reference` over the
+        prefill's own activations, scored on the device by
+        `engine.score()`. Requires `logprobs` and an engine with `score()`;
+        with echo, `max_new=0` is a pure scoring request that finishes
+        when its prefill does."""
         if logprobs is not None:
             if isinstance(logprobs, bool) or not isinstance(logprobs, int) \
                     or not 0 <= logprobs <= LOGPROBS_MAX_TOP:
@@ -163,9 +180,14 @@ class ContinuousBatcher:
             if not all(hasattr(e, "logprobs") for e in self.lanes):
                 raise ValueError("logprobs needs an engine with logprobs()")
             self._logprobs_seen = True
+        if echo:
+            if logprobs is None:
+                raise ValueError("echo needs logprobs to be set")
+            if not all(hasattr(e, "score") for e in self.lanes):
+                raise ValueError("echo needs an engine with score()")
         if len(prompt_ids) < 1:
             raise ValueError("prompt must contain at least one token")
-        if max_new < 1:
+        if max_new < 1 and not (echo and max_new == 0):
             raise ValueError("max_new must be >= 1")
         n_ctx = getattr(self.engine, "n_ctx", None)
         if n_ctx is not None and len(prompt_ids) + max_new > n_ctx:
@@ -175,12 +197,18 @@ class ContinuousBatcher:
         r = Request(rid=self._next_rid, prompt=list(map(int, prompt_ids)),
                     max_new=max_new, sampler=sampler,
                     eos_id=self.eos_id if eos_id is None else eos_id,
-                    logprobs=logprobs)
+                    logprobs=logprobs, echo=bool(echo))
+        if r.echo:
+            r.prompt_logprobs.append(None)
+            r.prompt_top.append(None)
         self._next_rid += 1
         self.queue.append(r)
         return r
 
-    def _admit(self) -> None:
+    def _admit(self) -> List[Request]:
+        """Returns the requests that finished during admission: pure
+        scoring requests (echo, max_new == 0) whose prefill completed."""
+        finished: List[Request] = []
         eng = self.engine  # n_ctx/bounds source; lanes share hparams
         n_ctx = getattr(eng, "n_ctx", 1 << 30)
         k = len(self.lanes)
@@ -199,13 +227,14 @@ class ContinuousBatcher:
             if len(r.prompt) > 1:
                 self.prefilling[r.slot] = r
             else:
-                self._activate(r)
+                self._prefilled(r, finished)
         # prefill as ONE concatenated (token, pos, seq) stream per lane
         # — the engine tiles any mixed-sequence stream internally, so
         # several prompts share each prefill launch; with prefill_chunk
         # set, each lane advances at most that many prompt tokens per
         # step and decode of OTHER requests interleaves
         budget_full = self.prefill_chunk
+        scored = []   # per lane with echo rows: _score_lane's result
         per_lane: List[List[Request]] = [[] for _ in range(k)]
         for slot in sorted(self.prefilling):
             per_lane[slot % k].append(self.prefilling[slot])
@@ -214,6 +243,7 @@ class ContinuousBatcher:
                 continue
             budget = budget_full
             toks, pos, seq = [], [], []
+            echo = []   # (request, first stream row, row count)
             for r in reqs:
                 end = len(r.prompt) - 1
                 take = end - r._pf_pos
@@ -222,6 +252,8 @@ class ContinuousBatcher:
                     budget -= take
                 if take <= 0:
                     continue
+                if r.echo:
+                    echo.append((r, len(toks), take))
                 toks += r.prompt[r._pf_pos:r._pf_pos + take]
                 pos += list(range(r._pf_pos, r._pf_pos + take))
                 seq += [r.slot // k] * take
@@ -241,12 +273,94 @@ class ContinuousBatcher:
                                  device=self._dev)
                 q = torch.tensor(seq, dtype=torch.int32,
                                  device=self._dev)
-                lane_eng.forward(lane_eng.embed(t), p, q)
+                y = lane_eng.forward(lane_eng.embed(t), p, q)
+                if echo:
+                    scored.append(self._score_lane(lane_eng, y, echo))
+        if scored:
+            if self._streams is not None:
+                for st in self._streams:
+                    torch.cuda.current_stream().wait_stream(st)
+            for item in scored:
+                self._record_echo(*item)
         for slot in list(self.prefilling):
             r = self.prefilling[slot]
             if r._pf_pos >= len(r.prompt) - 1:
                 del self.prefilling[slot]
-                self._activate(r)
+                self._prefilled(r, finished)
+        return finished
+
+    def _prefilled(self, r: Request, finished: List[Request]) -> None:
+        """The prompt body is in the KV cache: start decoding, or finish
+        a pure scoring request (max_new == 0) without activating it."""
+        if r.max_new > 0:
+            self._activate(r)
+            return
+        r.done = True
+        self.free.append(r.slot)
+        r.slot = -1
+        finished.append(r)
+
+    def _score_lane(self, eng, y, echo):
+        """Score the echo rows of one lane's prefill output `y` on the
+        current (the lane's) stream: stream row i of a request's span
+        holds prompt position _pf_pos_before + i and is scored against
+        the NEXT prompt token. One engine.score call over the gathered
+        rows; requests with logprobs >= 2 add logits() + logprobs() over
+        their rows for the further alternatives. Returns (echo, packed
+        [R, 3] device tensor lp | top_lp | top_id bits, n_top, packed
+        [R2, 2 n_top] or None, {echo index: first row in the second})."""
+        rows, targets = [], []
+        for r, first, take in echo:
+            p0 = r._pf_pos - take
+            rows += range(first, first + take)
+            targets += r.prompt[p0 + 1:p0 + take + 1]
+        dev = y.device
+        if rows != list(range(y.shape[0])):
+            y = y.index_select(0, torch.tensor(rows, dtype=torch.int32,
+                                               device=dev))
+        tg = torch.tensor(targets, dtype=torch.int32, device=dev)
+        lp, top_id, top_lp = eng.score(y, tg)
+        packed = torch.stack([lp, top_lp, top_id.view(torch.float32)],
+                             dim=1)
+        # further alternatives: existing parts over the same rows
+        sub, first2, n_top, at = [], {}, 0, 0
+        for ei, (r, first, take) in enumerate(echo):
+            if r.logprobs >= 2:
+                first2[ei] = len(sub)
+                sub += range(at, at + take)
+                n_top = max(n_top, r.logprobs)
+            at += take
+        more = None
+        if sub:
+            if len(sub) != y.shape[0]:
+                idx = torch.tensor(sub, dtype=torch.int32, device=dev)
+                y, tg = y.index_select(0, idx), tg.index_select(0, idx)
+            lg = eng.logits(y, all_logits=True)
+            _, ids, lps = eng.logprobs(lg, list(range(len(sub))), tg, n_top)
+            more = torch.cat([lps, ids.view(torch.float32)], dim=1)
+        return echo, packed, n_top, more, first2
+
+    def _record_echo(self, echo, packed, n_top, more, first2) -> None:
+        a = packed.cpu().numpy()
+        lp, top_lp = a[:, 0].tolist(), a[:, 1].tolist()
+        top_id = a[:, 2].copy().view("int32").tolist()
+        if more is not None:
+            m = more.cpu().numpy()
+            m_lp = m[:, :n_top].tolist()
+            m_id = m[:, n_top:].copy().view("int32").tolist()
+        at = 0
+        for ei, (r, _, take) in enumerate(echo):
+            for i in range(at, at + take):
+                r.prompt_logprobs.append(lp[i])
+                if r.logprobs >= 2:
+                    f = first2[ei] + i - at
+                    r.prompt_top.append(list(zip(m_id[f][:r.logprobs],
+                                                 m_lp[f][:r.logprobs])))
+                elif r.logprobs == 1:
+                    r.prompt_top.append([(top_id[i], top_lp[i])])
+                else:
+                    r.prompt_top.append([])
+            at += take
 
     def _activate(self, r: Request) -> None:
         r._next_tok = r.prompt[-1]
@@ -268,9 +382,9 @@ class ContinuousBatcher:
     def step(self) -> List[Request]:
         """Admit what fits, advance every active request one token;
         returns the requests that finished on this step."""
-        self._admit()
+        finished: List[Request] = self._admit()
         if not self.active:
-            return []
+            return finished
         self.steps_run += 1
         k = len(self.lanes)
         # one decode launch per lane, each on its own stream (CUDA)
@@ -325,7 +439,6 @@ class ContinuousBatcher:
             for st in self._streams:
                 torch.cuda.current_stream().wait_stream(st)
 
-        finished: List[Request] = []
         for reqs, drafts, greedy_ids, lg, sampled_ids, lp in work:
             if greedy_ids is not None and greedy_ids.device.type != "cpu":
                 greedy_ids = greedy_ids.cpu()

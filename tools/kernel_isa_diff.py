@@ -64,7 +64,9 @@ def kernels(src, arch):
     dem = subprocess.run(["c++filt"], input="\n".join(names), text=True,
                          capture_output=True, check=True).stdout.split("\n")
     # "void k<int=1>(args)" -> "k<1>": the arguments are not compared
-    short = [re.sub(r"^void |\(.*\)$", "", d).replace(
+    # (kernels in an anonymous namespace keep their bare name)
+    short = [re.sub(r"^void |\(.*\)$", "",
+                    d.replace("(anonymous namespace)::", "")).replace(
         "(WType)", "").replace("(GemmMode)", "") for d in dem]
     return {s: (body[n], meta[n]) for s, n in zip(short, names)}
 
