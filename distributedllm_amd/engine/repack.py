@@ -320,42 +320,51 @@ def repack_mfma(t: ggml.GGMLTensor, device):
     return _pack_bytes(*expand_kquant(t, device))
 
 
-def detile_mfma(mat, rows: int, cols: int) -> torch.Tensor:
-    """Inverse of repack_mfma: tiled weights -> plain f16 [rows, cols].
-    Test/debug utility, the independent reading of the layouts."""
+def detile_mfma(mat, rows: int, cols: int,
+                dtype=torch.half) -> torch.Tensor:
+    """Inverse of repack_mfma: tiled weights -> plain [rows, cols].
+    Test/debug utility, the independent reading of the layouts.
+
+    dtype = torch.half (default): alpha*n + beta computed in f32, then
+    rounded to f16 - two roundings. dtype = torch.float64: the same
+    expression in float64, not rounded (the products of an f16 scale and
+    an 8-bit integer plus an f16 offset are exact there), so a caller can
+    apply the single f16 rounding of the kernel's v_pk_fma_f16 itself."""
+    assert dtype in (torch.half, torch.float64), dtype
+    f = torch.float64 if dtype == torch.float64 else torch.float32
     data, sc, wt = mat
     if wt == W_F16:
         t = data[:rows * cols].view(torch.half)
         return (t.view(rows // 16, cols // 8, 16, 8)
-                .permute(0, 2, 1, 3).reshape(rows, cols))
+                .permute(0, 2, 1, 3).reshape(rows, cols)).to(dtype)
     R, nbp = rows // 16, padded_blocks(cols // 32)
     if wt == W_Q8B16:
         # [R,g4,hp,i,kb,2]: half-plane hp serves word-spans 2hp, 2hp+1
-        ab = (sc[:R * nbp * 64].view(R, nbp // 4, 2, 16, 4, 2).float()
+        ab = (sc[:R * nbp * 64].view(R, nbp // 4, 2, 16, 4, 2).to(f)
               .repeat_interleave(2, dim=2))
     else:
-        ab = sc[:R * nbp * 32].view(R, nbp // 4, 1, 16, 4, 2).float()
+        ab = sc[:R * nbp * 32].view(R, nbp // 4, 1, 16, 4, 2).to(f)
     alpha = ab[..., 0].unsqueeze(-1)              # [R,g4,ws|1,i,kb,1]
     beta = ab[..., 1].unsqueeze(-1)
     if wt in (W_Q4_0, W_Q4_1):
         qw = data[:R * nbp * 64].view(R, nbp // 4, 4, 16, 4)
         shifts = torch.tensor(_Q4_SHIFTS, device=data.device,
                               dtype=torch.int32)
-        n = ((qw.unsqueeze(-1) >> shifts) & 0xF).float()
+        n = ((qw.unsqueeze(-1) >> shifts) & 0xF).to(f)
         w = alpha * (n - 8.0) if wt == W_Q4_0 else alpha * n + beta
         # [R,g4,ws,i,kb,8] -> [R,i,g4,kb,ws,8] -> [rows, nbp*32]
         w = w.permute(0, 3, 1, 4, 2, 5).reshape(rows, nbp * 32)
-        return w[:, :cols].to(torch.half)
+        return w[:, :cols].to(dtype)
     assert wt in (W_Q8B, W_Q8B16), wt
     # u32 bytes are [w0,w2,w1,w3]: weight jj sits at byte [0,2,1,3][jj]
     qw = data[:R * nbp * 128].view(R, nbp // 4, 4, 16, 4, 2)
     bshift = torch.tensor([0, 16, 8, 24], device=data.device,
                           dtype=torch.int32)
-    u = ((qw.unsqueeze(-1) >> bshift) & 0xFF).float()
+    u = ((qw.unsqueeze(-1) >> bshift) & 0xFF).to(f)
     w = alpha.unsqueeze(-1) * (u - 128.0) + beta.unsqueeze(-1)
     # [R,g4,ws,i,kb,2,4] -> [R,i,g4,kb,ws,2,4] -> [rows, nbp*32]
     w = w.permute(0, 3, 1, 4, 2, 5, 6).reshape(rows, nbp * 32)
-    return w[:, :cols].to(torch.half)
+    return w[:, :cols].to(dtype)
 
 
 def random_tiles(wt: int, rows: int, cols: int, g: torch.Generator):

@@ -872,10 +872,290 @@ AttnResult attention_prefill(torch::Tensor q, torch::Tensor k_store,
     return r;
 }
 
+// ----------------------------------------------- dequant-GEMM test hooks
+// Direct entry points to the launchers of mfma_gemm.hip for tests/
+// test_gpu_gemm.py, in the spirit of the attention hooks above: every
+// buffer is allocated per call by the engine's own sizing rules (tiled
+// matrices through make_devmat2, side channels by the `side(cols)` rule of
+// the SliceEngine constructor at panel width jt_width(T), norm weights
+// through pad_normprep, sumsq buffers of T rounded up to 64 floats, the
+// slab at the maximum split of 8), and everything that could send a kernel
+// out of bounds is refused.
+//
+// dead_fill: after the input panel is staged with launch_prep_x, the dead
+// token columns t in [T, 16*jtw) of the live rows kc < cols/8 are
+// overwritten with this f16 bit pattern. Live outputs must not depend on
+// it. The K-pad rows stay zero as in the engine (they meet alpha = beta = 0
+// blocks and must be finite).
+
+constexpr int64_t kHookMaxT = 4096;
+
+int64_t side_numel(int64_t cols, int64_t jtw) {
+    return (((cols / 32 + 3) & ~(int64_t)3)) * 512 * jtw + kTailSlackSide;
+}
+
+DevMat2 mat_arg(const py::tuple& m, const char* name) {
+    TORCH_CHECK(m.size() == 5, name,
+                " must be (data, scales, wtype, rows, cols)");
+    const int64_t wt = m[2].cast<int64_t>();
+    const int64_t rows = m[3].cast<int64_t>();
+    const int64_t cols = m[4].cast<int64_t>();
+    TORCH_CHECK(rows >= 16 && rows <= ((int64_t)1 << 20) && cols >= 32 &&
+                    cols <= ((int64_t)1 << 16),
+                name, ": rows/cols out of range");
+    return make_devmat2(m[0].cast<torch::Tensor>(),
+                        m[1].cast<torch::Tensor>(), wt, rows, cols);
+}
+
+int check_panel_input(const torch::Tensor& x, int64_t cols,
+                      const char* name) {
+    check_f32(x, name);
+    TORCH_CHECK(x.dim() == 2 && x.size(1) == cols, name,
+                " must be [T, cols] with the matrix's cols");
+    TORCH_CHECK(x.size(0) >= 1 && x.size(0) <= kHookMaxT,
+                "token count out of range");
+    return (int)x.size(0);
+}
+
+int16_t check_dead_fill(int64_t dead_fill) {
+    TORCH_CHECK(dead_fill >= -32768 && dead_fill <= 65535,
+                "dead_fill must be a 16-bit pattern");
+    return (int16_t)(uint16_t)(dead_fill & 0xFFFF);
+}
+
+torch::Tensor check_norm_w(const torch::Tensor& w, int64_t cols) {
+    check_f32(w, "norm_w");
+    TORCH_CHECK(w.dim() == 1 && w.numel() == cols, "norm_w must be [cols]");
+    return pad_normprep(w);
+}
+
+struct Panel {
+    torch::Tensor prep, ss;
+    int jtw;
+};
+
+// x [T, cols] -> f16 panel + sumsq, then the dead columns filled
+Panel stage_panel(hipStream_t s, const torch::Tensor& x, int cols, int T,
+                  int16_t fill) {
+    auto dev = torch::TensorOptions().device(torch::kCUDA);
+    Panel p;
+    p.jtw = jt_width(T);
+    TORCH_CHECK(p.jtw * 16 >= T, "jt_width does not cover T");
+    p.prep = torch::zeros({side_numel(cols, p.jtw)}, dev.dtype(torch::kInt16));
+    p.ss = torch::zeros({((int64_t)T + 63) & ~(int64_t)63},
+                        dev.dtype(torch::kFloat32));
+    launch_prep_x(s, x.data_ptr<float>(), u16p(p.prep),
+                  p.ss.data_ptr<float>(), cols, T);
+    if (T < p.jtw * 16)
+        p.prep.narrow(0, 0, (int64_t)(cols / 8) * p.jtw * 128)
+            .view({cols / 8, (int64_t)p.jtw * 16, 8})
+            .slice(1, T, (int64_t)p.jtw * 16)
+            .fill_(fill);
+    return p;
+}
+
+torch::Tensor zero_side(int64_t cols, int64_t jtw) {
+    return torch::zeros(
+        {side_numel(cols, jtw)},
+        torch::TensorOptions().device(torch::kCUDA).dtype(torch::kInt16));
+}
+
+// y = y_in + mat . b through the wo / w2 routes. T <= 64: split = true is
+// GM_SLAB + launch_reduce_prep (the engine's rule: rows/16 even), split =
+// false GM_RES_SQ; T > 64: launch_gemm16_mt (split refused).
+// -> (y [T, rows] f32, xprep_out i16 flat, ss_out f32 [T up to 64], jtw)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, int64_t>
+gemm_residual(py::tuple mat, torch::Tensor b, torch::Tensor y_in, bool split,
+              int64_t dead_fill) {
+    DevMat2 m = mat_arg(mat, "mat");
+    const int T = check_panel_input(b, m.w.cols, "b");
+    check_f32(y_in, "y_in");
+    TORCH_CHECK(y_in.dim() == 2 && y_in.size(0) == T &&
+                    y_in.size(1) == m.w.rows,
+                "y_in must be [T, rows]");
+    const int16_t fill = check_dead_fill(dead_fill);
+    TORCH_CHECK(!split || T <= kMaxTokens,
+                "split-K is a decode route (T <= 64)");
+    TORCH_CHECK(!split || (m.w.rows / 16) % 2 == 0,
+                "the engine splits K only when rows/16 is even");
+    auto f32 = torch::TensorOptions().device(torch::kCUDA).dtype(
+        torch::kFloat32);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    Panel p = stage_panel(s, b, m.w.cols, T, fill);
+    auto y = y_in.clone();
+    auto xo = zero_side(m.w.rows, p.jtw);
+    auto sso = torch::zeros({((int64_t)T + 63) & ~(int64_t)63}, f32);
+    if (T > kMaxTokens) {
+        launch_gemm16_mt(s, m.w, u16p(p.prep), y.data_ptr<float>(), u16p(xo),
+                         sso.data_ptr<float>(), T);
+    } else if (split) {
+        const int ks = gemm16_ks(m.w.rows);
+        TORCH_CHECK(ks >= 1 && ks <= 8, "split factor out of range");
+        auto slab = torch::zeros(
+            {(int64_t)(m.w.rows / 16) * 8 * kMaxTokens * 16}, f32);
+        launch_gemm16(s, m.w, u16p(p.prep), nullptr, nullptr, 0.f,
+                      slab.data_ptr<float>(), nullptr, nullptr, T, GM_SLAB);
+        launch_reduce_prep(s, y.data_ptr<float>(), slab.data_ptr<float>(),
+                           ks, u16p(xo), sso.data_ptr<float>(), m.w.rows, T);
+    } else {
+        launch_gemm16(s, m.w, u16p(p.prep), nullptr, nullptr, 0.f,
+                      y.data_ptr<float>(), u16p(xo), sso.data_ptr<float>(),
+                      T, GM_RES_SQ);
+    }
+    return {y, xo, sso, (int64_t)p.jtw};
+}
+
+// logits [T, rows] = mat . rmsnorm(x) * norm_w: launch_prep_x +
+// GM_NORM_PLAIN, T <= 64
+torch::Tensor gemm_lmhead(py::tuple mat, torch::Tensor x,
+                          torch::Tensor norm_w, double eps,
+                          int64_t dead_fill) {
+    DevMat2 m = mat_arg(mat, "mat");
+    const int T = check_panel_input(x, m.w.cols, "x");
+    TORCH_CHECK(T <= kMaxTokens, "the lm_head takes at most ", kMaxTokens,
+                " rows per launch");
+    auto normprep = check_norm_w(norm_w, m.w.cols);
+    const int16_t fill = check_dead_fill(dead_fill);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    Panel p = stage_panel(s, x, m.w.cols, T, fill);
+    auto lg = torch::zeros(
+        {T, m.w.rows},
+        torch::TensorOptions().device(torch::kCUDA).dtype(torch::kFloat32));
+    launch_gemm16(s, m.w, u16p(p.prep), u16p(normprep),
+                  p.ss.data_ptr<float>(), (float)eps, lg.data_ptr<float>(),
+                  nullptr, nullptr, T, GM_NORM_PLAIN);
+    return lg;
+}
+
+// gprep = f16(silu(m1 . n) * (m3 . n)), n = rmsnorm(x) * norm_w, in the
+// side-channel layout: launch_ffn16 (T <= 64) / launch_ffn16_mt.
+// -> (gprep i16 flat, jtw)
+std::tuple<torch::Tensor, int64_t> ffn_gate(py::tuple m1, py::tuple m3,
+                                            torch::Tensor x,
+                                            torch::Tensor norm_w, double eps,
+                                            int64_t dead_fill) {
+    DevMat2 a = mat_arg(m1, "m1");
+    DevMat2 c = mat_arg(m3, "m3");
+    TORCH_CHECK(a.w.rows == c.w.rows && a.w.cols == c.w.cols &&
+                    a.w.wtype == c.w.wtype,
+                "m1 and m3 must agree in rows, cols and wtype");
+    const int T = check_panel_input(x, a.w.cols, "x");
+    auto normprep = check_norm_w(norm_w, a.w.cols);
+    const int16_t fill = check_dead_fill(dead_fill);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    Panel p = stage_panel(s, x, a.w.cols, T, fill);
+    auto g = zero_side(a.w.rows, p.jtw);
+    if (T > kMaxTokens)
+        launch_ffn16_mt(s, a.w, c.w, u16p(p.prep), u16p(normprep),
+                        p.ss.data_ptr<float>(), (float)eps, u16p(g), T);
+    else
+        launch_ffn16(s, a.w, c.w, u16p(p.prep), u16p(normprep),
+                     p.ss.data_ptr<float>(), (float)eps, u16p(g), T);
+    return {g, (int64_t)p.jtw};
+}
+
+// q [T, E] = rope(mq . n); rows pos[t] of slot seq[t] of k_store / v_store
+// get rope(mk . n) / mv . n in place. launch_qkv16 with a slab and
+// skip_finish = 0 (T <= 64: slab route + k_qkv_finish, or a fused route,
+// as qkv16_route decides) / launch_qkv16_mt.
+torch::Tensor qkv_project(py::tuple mq, py::tuple mk, py::tuple mv,
+                          torch::Tensor x, torch::Tensor norm_w, double eps,
+                          torch::Tensor k_store, torch::Tensor v_store,
+                          torch::Tensor pos, torch::Tensor seq,
+                          torch::Tensor inv_freq, int64_t n_head,
+                          int64_t n_head_kv, int64_t n_ctx, int64_t n_slots,
+                          int64_t dead_fill) {
+    DevMat2 q = mat_arg(mq, "mq");
+    DevMat2 k = mat_arg(mk, "mk");
+    DevMat2 v = mat_arg(mv, "mv");
+    const int E = q.w.rows;
+    TORCH_CHECK(q.w.cols == E && k.w.cols == E && v.w.cols == E,
+                "mq must be [E, E], mk and mv [Ekv, E]");
+    TORCH_CHECK(k.w.rows == v.w.rows, "mk and mv must agree in rows");
+    TORCH_CHECK(k.w.wtype == q.w.wtype && v.w.wtype == q.w.wtype,
+                "mq, mk and mv must share one wtype");
+    const int T = check_panel_input(x, E, "x");
+    TORCH_CHECK(n_head >= 1 && E % n_head == 0, "E not divisible by n_head");
+    const AttnDims d = check_attn_args(T, n_head, n_head_kv, E / n_head,
+                                       n_ctx, n_slots, k_store, v_store,
+                                       pos, seq);
+    TORCH_CHECK(d.E == E && d.Ekv == k.w.rows,
+                "head counts do not match the matrices");
+    // two tokens must not write the same cache row
+    {
+        auto key = (seq.to(torch::kCPU).to(torch::kInt64) * n_ctx +
+                    pos.to(torch::kCPU).to(torch::kInt64));
+        auto sorted = std::get<0>(key.sort());
+        for (int64_t i = 1; i < T; ++i)
+            TORCH_CHECK(sorted[i].item<int64_t>() !=
+                            sorted[i - 1].item<int64_t>(),
+                        "(seq, pos) pairs must be pairwise distinct");
+    }
+    check_f32(inv_freq, "inv_freq");
+    TORCH_CHECK(inv_freq.numel() == d.D / 2, "inv_freq must be [D/2]");
+    auto normprep = check_norm_w(norm_w, E);
+    const int16_t fill = check_dead_fill(dead_fill);
+    auto f32 = torch::TensorOptions().device(torch::kCUDA).dtype(
+        torch::kFloat32);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    Panel p = stage_panel(s, x, E, T, fill);
+    auto qb = torch::zeros({T, E}, f32);
+    if (T > kMaxTokens) {
+        launch_qkv16_mt(s, q.w, k.w, v.w, u16p(p.prep), u16p(normprep),
+                        p.ss.data_ptr<float>(), (float)eps,
+                        qb.data_ptr<float>(), h16(k_store), h16(v_store),
+                        pos.data_ptr<int>(), seq.data_ptr<int>(),
+                        inv_freq.data_ptr<float>(), E, d.Ekv, d.D, d.ctx, T);
+    } else {
+        TORCH_CHECK(qkv16_ks(E, d.Ekv) <= 8, "split factor out of range");
+        auto slab = torch::zeros(
+            {(int64_t)((E + 2 * d.Ekv) / 16) * 8 * kMaxTokens * 16}, f32);
+        launch_qkv16(s, q.w, k.w, v.w, u16p(p.prep), u16p(normprep),
+                     p.ss.data_ptr<float>(), (float)eps,
+                     qb.data_ptr<float>(), h16(k_store), h16(v_store),
+                     pos.data_ptr<int>(), seq.data_ptr<int>(),
+                     inv_freq.data_ptr<float>(), E, d.Ekv, d.D, d.ctx, T,
+                     slab.data_ptr<float>(), /*skip_finish=*/0);
+    }
+    return qb;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     // test hooks (see above), not serving API
+    m.def("gemm_residual", &gemm_residual, py::arg("mat"), py::arg("b"),
+          py::arg("y_in"), py::arg("split"), py::arg("dead_fill"));
+    m.def("gemm_lmhead", &gemm_lmhead, py::arg("mat"), py::arg("x"),
+          py::arg("norm_w"), py::arg("eps"), py::arg("dead_fill"));
+    m.def("ffn_gate", &ffn_gate, py::arg("m1"), py::arg("m3"), py::arg("x"),
+          py::arg("norm_w"), py::arg("eps"), py::arg("dead_fill"));
+    m.def("qkv_project", &qkv_project, py::arg("mq"), py::arg("mk"),
+          py::arg("mv"), py::arg("x"), py::arg("norm_w"), py::arg("eps"),
+          py::arg("k_store"), py::arg("v_store"), py::arg("pos"),
+          py::arg("seq"), py::arg("inv_freq"), py::arg("n_head"),
+          py::arg("n_head_kv"), py::arg("n_ctx"), py::arg("n_slots"),
+          py::arg("dead_fill"));
+    m.def("gemm16_ks", [](int64_t rows) {
+        return (int64_t)gemm16_ks((int)rows);
+    }, py::arg("rows"));
+    m.def("gemm16_plain_rt", [](int64_t rows) {
+        return (int64_t)gemm16_plain_rt((int)rows);
+    }, py::arg("rows"));
+    m.def("ffn16_rt", [](int64_t rows, int64_t T) {
+        return (int64_t)ffn16_rt((int)rows, (int)T);
+    }, py::arg("rows"), py::arg("T"));
+    m.def("gemm16_mt_rt", [](int64_t rows, int64_t T) {
+        return (int64_t)gemm16_mt_rt((int)rows, (int)T);
+    }, py::arg("rows"), py::arg("T"));
+    m.def("qkv16_route", [](int64_t E, int64_t Ekv, int64_t T,
+                            bool has_slab) {
+        return (int64_t)qkv16_route((int)E, (int)Ekv, (int)T,
+                                    has_slab ? 1 : 0);
+    }, py::arg("E"), py::arg("Ekv"), py::arg("T"), py::arg("has_slab"));
+    m.def("qkv16_mt_rt", [](int64_t E, int64_t Ekv, int64_t T) {
+        return (int64_t)qkv16_mt_rt((int)E, (int)Ekv, (int)T);
+    }, py::arg("E"), py::arg("Ekv"), py::arg("T"));
     m.def("attention_decode", &attention_decode, py::arg("q"),
           py::arg("k_store"), py::arg("v_store"), py::arg("pos"),
           py::arg("seq"), py::arg("n_head"), py::arg("n_head_kv"),

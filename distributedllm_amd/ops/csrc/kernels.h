@@ -46,6 +46,20 @@ enum GemmMode { GM_RES_SQ = 1, GM_NORM_PLAIN = 2, GM_SLAB = 4 };
 // split-K factor used by GM_SLAB (shared with the reducer)
 int gemm16_ks(int rows);
 
+// Route selectors: which instantiation each launcher below runs, as plain
+// host functions of the matrix and token counts (exported to the tests).
+//   gemm16_plain_rt  lm_head GM_NORM_PLAIN: row tiles per wave, 1 | 2 | 4
+//   ffn16_rt         launch_ffn16 (T <= 64) / launch_ffn16_mt: 1 | 2
+//   gemm16_mt_rt     launch_gemm16_mt: 1 | 2
+//   qkv16_route      launch_qkv16 (T <= 64): 0 slab split-K (RT=2),
+//                    1 fused RT=1, 2 fused RT=2
+//   qkv16_mt_rt      launch_qkv16_mt: 1 | 2
+int gemm16_plain_rt(int rows);
+int ffn16_rt(int rows, int T);
+int gemm16_mt_rt(int rows, int T);
+int qkv16_route(int E, int Ekv, int T, int has_slab);
+int qkv16_mt_rt(int E, int Ekv, int T);
+
 // y[t] += sum of ks slab partials, then sumsq + f16 xprep of the result
 void launch_reduce_prep(hipStream_t s, float* y, const float* slab, int ks,
                         unsigned short* xprep, float* ss, int cols, int T);

@@ -1254,6 +1254,55 @@ int gemm16_ks(int rows) {
     return ks;
 }
 
+// ------------------------------------------------------ route selectors
+// Which instantiation a launcher runs depends on the matrix and token
+// counts alone. The rules live here, one plain function each, so the
+// launchers and the tests (which export them) read the same decision.
+
+// lm_head (GM_NORM_PLAIN): thousands of row tiles re-read the same B
+// panel; RT divides that L2 traffic while the grid still fills
+int gemm16_plain_rt(int rows) {
+    const int R = rows / 16;
+    if (R % 4 == 0 && R / 4 >= 448) return 4;
+    if (R % 2 == 0 && R >= 1024) return 2;
+    return 1;
+}
+
+// ffn gate, decode (T <= 64) and large-M
+int ffn16_rt(int rows, int T) {
+    const int MT = (T <= 64) ? 1 : (T + 63) >> 6;
+    return rt2_fills(rows / 16, MT) ? 2 : 1;
+}
+
+// wo / w2 large-M (T > 64)
+int gemm16_mt_rt(int rows, int T) {
+    return rt2_fills(rows >> 4, (T + 63) >> 6) ? 2 : 1;
+}
+
+// RT=2 needs an even tile count in each of the three matrices
+static inline bool qkv_rt2_ok(int E, int Ekv) {
+    return ((E >> 4) % 2 == 0) && ((Ekv >> 4) % 2 == 0);
+}
+
+// decode qkv (T <= 64): 0 = RT=2 slab split-K when the fused grid would
+// underfill the chip, 2 = fused RT=2 (big models: halves the B-panel
+// re-read while the halved grid still fills), 1 = fused RT=1
+int qkv16_route(int E, int Ekv, int T, int has_slab) {
+    (void)T;  // the decode routes do not depend on the token count
+    const int tiles3 = (E + 2 * Ekv) >> 4;
+    const bool rt2_ok = qkv_rt2_ok(E, Ekv);
+    if (has_slab && tiles3 < 1024 && rt2_ok) return 0;
+    if (rt2_ok && rt2_fills(tiles3, 1)) return 2;
+    return 1;
+}
+
+// large-M qkv: RT=2 halves the B-panel reads + norm-build VALU per MFMA
+// as long as the halved grid still fills the chip
+int qkv16_mt_rt(int E, int Ekv, int T) {
+    const int tiles3 = (E + 2 * Ekv) >> 4;
+    return (qkv_rt2_ok(E, Ekv) && rt2_fills(tiles3, (T + 63) >> 6)) ? 2 : 1;
+}
+
 void launch_reduce_prep(hipStream_t s, float* y, const float* slab, int ks,
                         unsigned short* xprep, float* ss, int cols, int T) {
     const int want = (128 + T - 1) / max(T, 1);  // see microbench note
@@ -1295,14 +1344,13 @@ void launch_gemm16(hipStream_t s, const WMat2& w,
                                dim3(BLOCK), 0, s, w, bprep, normprep, ss_in,
                                eps, y, xprep_out, ss_out, T);
         else {  // GM_NORM_PLAIN
-            // lm_head: thousands of row tiles re-read the same B panel —
-            // RT divides that L2 traffic while the grid still fills
-            if (R % 4 == 0 && R / 4 >= 448)
+            const int rt = gemm16_plain_rt(w.rows);
+            if (rt == 4)
                 hipLaunchKernelGGL((k_gemm16<WTc, GM_NORM_PLAIN, JTc, 4>),
                                    dim3(R / 4), dim3(BLOCK), 0, s, w, bprep,
                                    normprep, ss_in, eps, y, xprep_out,
                                    ss_out, T);
-            else if (R % 2 == 0 && R >= 1024)
+            else if (rt == 2)
                 hipLaunchKernelGGL((k_gemm16<WTc, GM_NORM_PLAIN, JTc, 2>),
                                    dim3(R / 2), dim3(BLOCK), 0, s, w, bprep,
                                    normprep, ss_in, eps, y, xprep_out,
@@ -1323,9 +1371,8 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
                  const float* inv_freq, int E, int Ekv, int D, int n_ctx,
                  int T, float* slab, int skip_finish) {
     const int tiles3 = (E + 2 * Ekv) >> 4;
-    const bool rt2_ok = ((E >> 4) % 2 == 0) && ((Ekv >> 4) % 2 == 0);
-    // slab split-K + RT=2 path when the fused grid underfills the chip
-    if (slab != nullptr && tiles3 < 1024 && rt2_ok) {
+    const int route = qkv16_route(E, Ekv, T, slab != nullptr);
+    if (route == 0) {  // slab split-K + RT=2
         // RT=2 measured best (RT=4 loses ~3%: fill drops below 2/CU)
         const int ks = qkv16_ks(E, Ekv);
         const dim3 grid(tiles3 / 2, ks);
@@ -1342,9 +1389,7 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
         }
         return 1;
     }
-    if (rt2_ok && rt2_fills(tiles3, 1)) {
-        // big models: RT=2 fused — halves the B-panel re-read while the
-        // halved grid still fills the chip
+    if (route == 2) {
         const dim3 grid(tiles3 / 2);
         DISPATCH_WT2(wq.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
             (k_qkv16<WTc, JTc, 2>), grid, dim3(BLOCK), 0, s, wq, wk, wv,
@@ -1366,7 +1411,7 @@ void launch_ffn16(hipStream_t s, const WMat2& w1, const WMat2& w3,
                   const unsigned short* normprep, const float* ss_in,
                   float eps, unsigned short* gprep, int T) {
     const int tilesF = w1.rows / 16;
-    if (rt2_fills(tilesF, 1)) {
+    if (ffn16_rt(w1.rows, T) == 2) {
         const dim3 grid(tilesF / 2);
         DISPATCH_WT2(w1.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
             (k_ffn16<WTc, JTc, 2>), grid, dim3(BLOCK), 0, s, w1, w3, xprep,
@@ -1390,10 +1435,7 @@ void launch_qkv16_mt(hipStream_t s, const WMat2& wq, const WMat2& wk,
     const int MT = (T + 63) >> 6;
     const int jtw = jt_width(T);
     const int tiles3 = (E + 2 * Ekv) >> 4;
-    const bool rt2_ok = ((E >> 4) % 2 == 0) && ((Ekv >> 4) % 2 == 0);
-    // RT=2 halves the B-panel reads + norm-build VALU per MFMA as long
-    // as the halved grid still fills the chip
-    if (rt2_ok && rt2_fills(tiles3, MT)) {
+    if (qkv16_mt_rt(E, Ekv, T) == 2) {
         const dim3 grid(xcd_grid(tiles3 / 2, MT));
         DISPATCH_WT2(wq.wtype, hipLaunchKernelGGL(
             (k_qkv16<WTc, 4, 2, true>), grid, dim3(BLOCK), 0, s, wq, wk, wv,
@@ -1415,7 +1457,7 @@ void launch_gemm16_mt(hipStream_t s, const WMat2& w,
     const int MT = (T + 63) >> 6;
     const int jtw = jt_width(T);
     const int R = w.rows >> 4;
-    if (rt2_fills(R, MT)) {
+    if (gemm16_mt_rt(w.rows, T) == 2) {
         const dim3 grid(xcd_grid(R / 2, MT));
         DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
             (k_gemm16_mt<WTc, 4, 2>), grid, dim3(BLOCK), 0, s, w, bprep, y,
@@ -1435,7 +1477,7 @@ void launch_ffn16_mt(hipStream_t s, const WMat2& w1, const WMat2& w3,
     const int MT = (T + 63) >> 6;
     const int jtw = jt_width(T);
     const int R = w1.rows >> 4;
-    if (rt2_fills(R, MT)) {
+    if (ffn16_rt(w1.rows, T) == 2) {
         const dim3 grid(xcd_grid(R / 2, MT));
         DISPATCH_WT2(w1.wtype, hipLaunchKernelGGL(
             (k_ffn16<WTc, 4, 2, true>), grid, dim3(BLOCK), 0, s, w1, w3,

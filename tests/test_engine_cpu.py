@@ -113,6 +113,7 @@ def test_detile_inverts_repack():
     CPU tensors) then detile reproduces the codec's dequantized weights
     (f16-rounded) — this is the CPU-side proof that the layouts the
     prefill/decode kernels stream carry the exact quantized values."""
+    import numpy as np
     import torch
     import repack_cases as RC
     from distributedllm_amd.engine.repack import detile_mfma, repack_mfma
@@ -146,6 +147,15 @@ def test_detile_inverts_repack():
         tol = 4e-3 * want.abs().max().item() + 1e-6
         err = (got - want).abs().max().item()
         assert err <= tol, (ggml.TYPE_NAMES[t.gtype], t.name, err, tol)
+        # float64 detile, rounded once: the default (f32 arithmetic, then
+        # f16: two roundings) is within one f16 ulp of it
+        once = detile_mfma(mat, rows, cols, torch.float64).to(torch.half)
+        twice = detile_mfma(mat, rows, cols)
+        assert once.dtype == twice.dtype == torch.half
+        a, b = once.numpy(), twice.numpy()
+        ulp = np.spacing(np.maximum(np.abs(a), np.abs(b))).astype(np.float64)
+        assert (np.abs(a.astype(np.float64) - b.astype(np.float64))
+                <= ulp).all(), (ggml.TYPE_NAMES[t.gtype], t.name)
 
 
 def _check_group(group):
