@@ -42,6 +42,21 @@ constexpr int64_t kTailSlackAB = 128;    // f16 elements (256 B)
 constexpr int64_t kTailSlackF16 = 2048;  // f16 elements (4 KiB)
 constexpr int64_t kTailSlackSide = 8192; // int16 elements (16 KiB)
 
+// Buffer sizing rules of the MFMA path, shared by the engine and the test
+// hooks. Side channel [kc][jtw][16][8] f16 for a K dimension of `cols` at
+// panel width jtw: the PADDED K-block count (q4 wide-load groups of 4).
+int64_t side_numel(int64_t cols, int64_t jtw) {
+    return ((cols / 32 + 3) & ~(int64_t)3) * 512 * jtw + kTailSlackSide;
+}
+// split-K partial slabs f32 [tiles][ks][64][16]; allocations take the
+// maximum split of 8
+constexpr int64_t kMaxSplit = 8;
+int64_t slab_numel(int64_t tiles, int64_t ks = kMaxSplit) {
+    return tiles * ks * kMaxTokens * 16;
+}
+// sumsq channel of a T-token launch: whole 64-token groups
+int64_t sumsq_numel(int64_t T) { return (T + 63) & ~(int64_t)63; }
+
 struct DevMat {  // legacy scalar-path matrix (W_F32 models)
     torch::Tensor data, scales;
     WMat w{};
@@ -208,30 +223,22 @@ class SliceEngine {
         qb_ = torch::empty({maxP_, E_}, f32);
         ab_ = torch::empty({maxP_, E_}, f32);
         ffb_ = torch::empty({kMaxTokens, F_}, f32);
-        // MFMA-path side channels
-        // side channels sized for the PADDED K-block count (q4 wide-load
-        // groups of 4 blocks) and zero-filled: the pad region is consumed
-        // by alpha=0 weight blocks but must hold finite f16 values.
-        // Token-panel width = jt_width(maxP_) 16-token tiles — the decode
-        // path uses the first 4 tiles of the same buffers; layout
-        // [kc][jtw][16][8] f16
+        // MFMA-path side channels (side_numel), zero-filled: the pad
+        // region is consumed by alpha=0 weight blocks but must hold finite
+        // f16 values. Token-panel width = jt_width(maxP_) 16-token tiles —
+        // the decode path uses the first 4 tiles of the same buffers
         const int64_t jtwp = jt_width(maxP_);
-        auto side = [&](int cols) {
-            return (int64_t)(((cols / 32 + 3) & ~3)) * 512 * jtwp +
-                   kTailSlackSide;
-        };
-        xprep_ = torch::zeros({side(E_)}, u16);
-        aprep_ = torch::zeros({side(E_)}, u16);
-        gprep_ = torch::zeros({side(F_)}, u16);
+        xprep_ = torch::zeros({side_numel(E_, jtwp)}, u16);
+        aprep_ = torch::zeros({side_numel(E_, jtwp)}, u16);
+        gprep_ = torch::zeros({side_numel(F_, jtwp)}, u16);
         ss_attn_ = torch::zeros({(int64_t)(L_ + 1) * ssw_}, f32);
         ss_ffn_ = torch::zeros({(int64_t)L_ * ssw_}, f32);
-        ss_tmp_ = torch::zeros({kMaxTokens}, f32);
+        ss_tmp_ = torch::zeros({sumsq_numel(kMaxTokens)}, f32);
         argmax_keys_ = torch::zeros({maxP_}, dev.dtype(torch::kInt64));
         // split-K partial slabs: sized for the largest user — qkv
-        // (3E/16 tiles), ffn (2F/16), wo/w2 (E/16) — at the max split of 8
-        const int64_t slab_tiles =
-            std::max<int64_t>({3 * (E_ / 16), 2 * (F_ / 16), E_ / 16});
-        slab_ = torch::zeros({slab_tiles * 8 * kMaxTokens * 16}, f32);
+        // (3E/16 tiles), ffn (2F/16), wo/w2 (E/16)
+        slab_ = torch::zeros({slab_numel(std::max<int64_t>(
+            {3 * (E_ / 16), 2 * (F_ / 16), E_ / 16}))}, f32);
     }
 
     void set_layer(int64_t li, torch::Tensor attn_norm,
@@ -352,58 +359,27 @@ class SliceEngine {
         // zero the atomic sumsq slots, then stage x into the side channel
         (void)hipMemsetAsync(ssa, 0, sizeof(float) * (L_ + 1) * ssw_, s);
         (void)hipMemsetAsync(ssf, 0, sizeof(float) * L_ * ssw_, s);
-        launch_prep_x(s, xp, xprep, ssa, E_, T);
-        if (T > kMaxTokens) {
-            // large-M path: launch_*_mt cover all T tokens in one
-            // launch per op (XCD-grouped token tiles), the whole layer
-            // loop sequenced here in C++ — no host tiling, no library
-            // GEMMs, q4 tiles read directly. Serves BOTH prompt prefill
-            // and wide batched decode (decode=true: every token its own
-            // sequence — weights and dequant are paid ONCE for the whole
-            // batch instead of once per 64-token lane): only the
-            // attention kernel differs — 16-query tiles are spans for
-            // prefill, per-token streaming for the distinct-sequence
-            // decode shape.
-            static const bool dbg_sync = [] {
-                const char* v = std::getenv("DLLM_DEBUG_SYNC");
-                return v && v[0] == '1';
-            }();
-            auto ck = [&](const char* what, int li2) {
-                if (!dbg_sync) return;
-                hipError_t e = hipStreamSynchronize(s);
-                fprintf(stderr, "[dbg] L%d %s: %s\n", li2, what,
-                        hipGetErrorString(e));
-            };
-            for (int li = 0; li < L_; ++li) {
-                Layer& l = layers_[li];
-                __half* kc = kbase + (size_t)li * layer_stride;
-                __half* vc = vbase + (size_t)li * layer_stride;
-                launch_qkv16_mt(s, l.mq.w, l.mk.w, l.mv.w, xprep,
-                                u16p(l.attn_normprep), ssa + li * ssw_,
-                                eps_, qb, kc, vc, pp, sp, ifr, E_, EK_,
-                                D_, ctx_, T);
-                ck("qkv_mt", li);
-                if (decode)
-                    launch_attention(s, qb, kc, vc, ab, aprep, pp, sp, T,
-                                     H_, E_, EK_, D_, ctx_, nullptr, 0,
-                                     ifr);
-                else
-                    launch_attn_prefill(s, qb, kc, vc, ab, aprep, pp, sp,
-                                        T, H_, E_, EK_, D_, ctx_);
-                ck("attn", li);
-                launch_gemm16_mt(s, l.mo.w, aprep, xp, xprep,
-                                 ssf + li * ssw_, T);
-                ck("wo", li);
-                launch_ffn16_mt(s, l.m1.w, l.m3.w, xprep,
-                                u16p(l.ffn_normprep), ssf + li * ssw_,
-                                eps_, gprep, T);
-                ck("ffn", li);
-                launch_gemm16_mt(s, l.m2.w, gprep, xp, xprep,
-                                 ssa + (li + 1) * ssw_, T);
-                ck("w2", li);
-            }
-            return x;
-        }
+        launch_prep_x(s, xp, xprep, ssa, E_, T, jt_width(T));
+        // One layer loop for every T, sequenced here in C++ — no host
+        // tiling, no library GEMMs, q4 tiles read directly. The launchers
+        // pick decode or large-M kernels by T; large-M (more than 64 tokens)
+        // serves BOTH prompt prefill and wide batched decode (decode=true:
+        // every token its own sequence — weights and dequant are paid
+        // ONCE for the whole batch instead of once per 64-token lane).
+        static const bool split_ok = !std::getenv("DLLM_NO_SPLITK");
+        // per-launch error probe; must not be set under graph capture
+        // (it synchronizes the stream)
+        static const bool dbg_sync = [] {
+            const char* v = std::getenv("DLLM_DEBUG_SYNC");
+            return v && v[0] == '1';
+        }();
+        auto ck = [&](const char* what, int li) {
+            if (!dbg_sync) return;
+            hipError_t e = hipStreamSynchronize(s);
+            fprintf(stderr, "[dbg] L%d %s: %s\n", li, what,
+                    hipGetErrorString(e));
+        };
+        float* slab = slab_.data_ptr<float>();
         for (int li = 0; li < L_; ++li) {
             Layer& l = layers_[li];
             __half* kc = kbase + (size_t)li * layer_stride;
@@ -411,45 +387,30 @@ class SliceEngine {
             const int slab_used = launch_qkv16(
                 s, l.mq.w, l.mk.w, l.mv.w, xprep, u16p(l.attn_normprep),
                 ssa + li * ssw_, eps_, qb, kc, vc, pp, sp, ifr, E_, EK_,
-                D_, ctx_, T, slab_.data_ptr<float>(),
-                /*skip_finish=*/decode ? 1 : 0);
-            const bool fuse = decode && slab_used;
-            launch_attention(s, qb, kc, vc, ab, aprep, pp, sp, T, H_, E_,
-                             EK_, D_, ctx_,
-                             fuse ? slab_.data_ptr<float>() : nullptr,
-                             fuse ? qkv16_ks(E_, EK_) : 0, ifr);
-            // wo/w2 tile count (E/16) alone underfills 256 CUs — split K
-            // across grid.y into plain-stored slabs, then one fused
-            // reduce+residual+sumsq+xprep pass per matrix (no atomics;
-            // the kernel boundary provides slab visibility).
-            static const bool no_split = std::getenv("DLLM_NO_SPLITK");
-            // slab split-K + RT=2 wo/w2 wins at every model size tested
-            const bool split = !no_split && (E_ / 16) % 2 == 0;
-            float* slab = slab_.data_ptr<float>();
-            const int ks = gemm16_ks(E_);
-            if (split) {
-                launch_gemm16(s, l.mo.w, aprep, nullptr, nullptr, eps_,
-                              slab, nullptr, nullptr, T, GM_SLAB);
-                launch_reduce_prep(s, xp, slab, ks, xprep,
-                                   ssf + li * ssw_, E_, T);
+                D_, ctx_, T, slab, /*skip_finish=*/decode ? 1 : 0);
+            ck("qkv", li);
+            // 16-query tiles are spans for prefill; the distinct-sequence
+            // decode shape streams per token at any T, fused with the
+            // un-combined qkv slabs when the slab route ran
+            if (T > kMaxTokens && !decode) {
+                launch_attn_prefill(s, qb, kc, vc, ab, aprep, pp, sp, T, H_,
+                                    E_, EK_, D_, ctx_);
             } else {
-                launch_gemm16(s, l.mo.w, aprep, nullptr, nullptr, eps_, xp,
-                              xprep, ssf + li * ssw_, T, GM_RES_SQ);
+                const bool fuse = decode && slab_used;
+                launch_attention(s, qb, kc, vc, ab, aprep, pp, sp, T, H_,
+                                 E_, EK_, D_, ctx_, fuse ? slab : nullptr,
+                                 fuse ? qkv16_ks(E_, EK_) : 0, ifr);
             }
-            // ffn stays fused: a slab+finish variant measured slower at
-            // every split/occupancy combination tried and was removed
+            ck("attn", li);
+            launch_gemm16_residual(s, l.mo.w, aprep, xp, xprep,
+                                   ssf + li * ssw_, T, slab, split_ok);
+            ck("wo", li);
             launch_ffn16(s, l.m1.w, l.m3.w, xprep, u16p(l.ffn_normprep),
                          ssf + li * ssw_, eps_, gprep, T);
-            if (split) {
-                launch_gemm16(s, l.m2.w, gprep, nullptr, nullptr, eps_,
-                              slab, nullptr, nullptr, T, GM_SLAB);
-                launch_reduce_prep(s, xp, slab, ks, xprep,
-                                   ssa + (li + 1) * ssw_, E_, T);
-            } else {
-                launch_gemm16(s, l.m2.w, gprep, nullptr, nullptr, eps_, xp,
-                              xprep, ssa + (li + 1) * ssw_, T,
-                              GM_RES_SQ);
-            }
+            ck("ffn", li);
+            launch_gemm16_residual(s, l.m2.w, gprep, xp, xprep,
+                                   ssa + (li + 1) * ssw_, T, slab, split_ok);
+            ck("w2", li);
         }
         return x;
     }
@@ -485,11 +446,10 @@ class SliceEngine {
         if (out_mfma_) {
             (void)hipMemsetAsync(ss_tmp_.data_ptr(), 0, sizeof(float) * T, s);
             launch_prep_x(s, xin.data_ptr<float>(), u16p(xprep_),
-                          ss_tmp_.data_ptr<float>(), E_, T);
-            launch_gemm16(s, mout_.w, u16p(xprep_), u16p(final_normprep_),
+                          ss_tmp_.data_ptr<float>(), E_, T, jt_width(T));
+            launch_lmhead(s, mout_.w, u16p(xprep_), u16p(final_normprep_),
                           ss_tmp_.data_ptr<float>(), eps_,
-                          lg.data_ptr<float>(), nullptr, nullptr, T,
-                          GM_NORM_PLAIN);
+                          lg.data_ptr<float>(), T);
         } else {
             launch_rmsnorm(s, xin.data_ptr<float>(),
                            final_norm_.data_ptr<float>(),
@@ -613,8 +573,7 @@ class SliceEngine {
             // first use: engines that never score allocate nothing. The
             // partial count is largest where RT is smallest, at T = 1.
             const int64_t pmax = V_ / (16 * lmhead_score_rt(V_, 1));
-            const int64_t ssn = ((int64_t)maxP_ + 63) & ~(int64_t)63;
-            ss_score_ = torch::zeros({ssn}, f32);
+            ss_score_ = torch::zeros({sumsq_numel(maxP_)}, f32);
             score_key_ = torch::zeros({(int64_t)maxP_ * pmax},
                                       dev.dtype(torch::kInt64));
             score_sum_ = torch::zeros({(int64_t)maxP_ * pmax}, f32);
@@ -631,7 +590,8 @@ class SliceEngine {
         auto* pkey =
             reinterpret_cast<unsigned long long*>(score_key_.data_ptr());
         (void)hipMemsetAsync(ss, 0, sizeof(float) * ss_score_.numel(), s);
-        launch_prep_x_score(s, x.data_ptr<float>(), u16p(xprep_), ss, E_, T);
+        launch_prep_x(s, x.data_ptr<float>(), u16p(xprep_), ss, E_, T,
+                      score_jt_width(T));
         launch_lmhead_score(s, mout_.w, u16p(xprep_), u16p(final_normprep_),
                             ss, eps_, targets.data_ptr<int>(), pkey,
                             score_sum_.data_ptr<float>(),
@@ -840,8 +800,7 @@ AttnResult attention_decode_fused(torch::Tensor slab, torch::Tensor k_store,
                     "seq values must be pairwise distinct");
     const int ks = qkv16_ks(d.E, d.Ekv);
     check_f32(slab, "slab");
-    TORCH_CHECK(slab.numel() == (int64_t)((d.E + 2 * d.Ekv) / 16) * ks *
-                                    kMaxTokens * 16,
+    TORCH_CHECK(slab.numel() == slab_numel((d.E + 2 * d.Ekv) / 16, ks),
                 "slab must be f32[(E+2Ekv)/16][ks][64][16]");
     check_f32(inv_freq, "inv_freq");
     TORCH_CHECK(inv_freq.numel() == d.D / 2, "inv_freq must be [D/2]");
@@ -876,11 +835,11 @@ AttnResult attention_prefill(torch::Tensor q, torch::Tensor k_store,
 // Direct entry points to the launchers of mfma_gemm.hip for tests/
 // test_gpu_gemm.py, in the spirit of the attention hooks above: every
 // buffer is allocated per call by the engine's own sizing rules (tiled
-// matrices through make_devmat2, side channels by the `side(cols)` rule of
-// the SliceEngine constructor at panel width jt_width(T), norm weights
-// through pad_normprep, sumsq buffers of T rounded up to 64 floats, the
-// slab at the maximum split of 8), and everything that could send a kernel
-// out of bounds is refused.
+// matrices through make_devmat2, side channels by side_numel at panel
+// width jt_width(T), norm weights through pad_normprep, sumsq buffers by
+// sumsq_numel, the slab by slab_numel at the maximum split), and everything
+// that could send a kernel out of bounds is refused. The hooks call the
+// launchers the engine calls, so the route code under test is the engine's.
 //
 // dead_fill: after the input panel is staged with launch_prep_x, the dead
 // token columns t in [T, 16*jtw) of the live rows kc < cols/8 are
@@ -889,10 +848,6 @@ AttnResult attention_prefill(torch::Tensor q, torch::Tensor k_store,
 // blocks and must be finite).
 
 constexpr int64_t kHookMaxT = 4096;
-
-int64_t side_numel(int64_t cols, int64_t jtw) {
-    return (((cols / 32 + 3) & ~(int64_t)3)) * 512 * jtw + kTailSlackSide;
-}
 
 DevMat2 mat_arg(const py::tuple& m, const char* name) {
     TORCH_CHECK(m.size() == 5, name,
@@ -942,10 +897,9 @@ Panel stage_panel(hipStream_t s, const torch::Tensor& x, int cols, int T,
     p.jtw = jt_width(T);
     TORCH_CHECK(p.jtw * 16 >= T, "jt_width does not cover T");
     p.prep = torch::zeros({side_numel(cols, p.jtw)}, dev.dtype(torch::kInt16));
-    p.ss = torch::zeros({((int64_t)T + 63) & ~(int64_t)63},
-                        dev.dtype(torch::kFloat32));
+    p.ss = torch::zeros({sumsq_numel(T)}, dev.dtype(torch::kFloat32));
     launch_prep_x(s, x.data_ptr<float>(), u16p(p.prep),
-                  p.ss.data_ptr<float>(), cols, T);
+                  p.ss.data_ptr<float>(), cols, T, p.jtw);
     if (T < p.jtw * 16)
         p.prep.narrow(0, 0, (int64_t)(cols / 8) * p.jtw * 128)
             .view({cols / 8, (int64_t)p.jtw * 16, 8})
@@ -960,9 +914,9 @@ torch::Tensor zero_side(int64_t cols, int64_t jtw) {
         torch::TensorOptions().device(torch::kCUDA).dtype(torch::kInt16));
 }
 
-// y = y_in + mat . b through the wo / w2 routes. T <= 64: split = true is
-// GM_SLAB + launch_reduce_prep (the engine's rule: rows/16 even), split =
-// false GM_RES_SQ; T > 64: launch_gemm16_mt (split refused).
+// y = y_in + mat . b through launch_gemm16_residual, split passed as
+// split_ok. split = true is refused unless gemm16_res_route then takes the
+// slab route 0 (T <= 64 and rows/16 even), so split names the route.
 // -> (y [T, rows] f32, xprep_out i16 flat, ss_out f32 [T up to 64], jtw)
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, int64_t>
 gemm_residual(py::tuple mat, torch::Tensor b, torch::Tensor y_in, bool split,
@@ -974,39 +928,29 @@ gemm_residual(py::tuple mat, torch::Tensor b, torch::Tensor y_in, bool split,
                     y_in.size(1) == m.w.rows,
                 "y_in must be [T, rows]");
     const int16_t fill = check_dead_fill(dead_fill);
-    TORCH_CHECK(!split || T <= kMaxTokens,
-                "split-K is a decode route (T <= 64)");
-    TORCH_CHECK(!split || (m.w.rows / 16) % 2 == 0,
-                "the engine splits K only when rows/16 is even");
+    TORCH_CHECK(!split || gemm16_res_route(m.w.rows, T, 1) == 0,
+                "split-K is a decode route (T <= 64), taken only when "
+                "rows/16 is even");
+    TORCH_CHECK(gemm16_ks(m.w.rows) <= kMaxSplit,
+                "split factor out of range");
     auto f32 = torch::TensorOptions().device(torch::kCUDA).dtype(
         torch::kFloat32);
     hipStream_t s = c10::hip::getCurrentHIPStream().stream();
     Panel p = stage_panel(s, b, m.w.cols, T, fill);
     auto y = y_in.clone();
     auto xo = zero_side(m.w.rows, p.jtw);
-    auto sso = torch::zeros({((int64_t)T + 63) & ~(int64_t)63}, f32);
-    if (T > kMaxTokens) {
-        launch_gemm16_mt(s, m.w, u16p(p.prep), y.data_ptr<float>(), u16p(xo),
-                         sso.data_ptr<float>(), T);
-    } else if (split) {
-        const int ks = gemm16_ks(m.w.rows);
-        TORCH_CHECK(ks >= 1 && ks <= 8, "split factor out of range");
-        auto slab = torch::zeros(
-            {(int64_t)(m.w.rows / 16) * 8 * kMaxTokens * 16}, f32);
-        launch_gemm16(s, m.w, u16p(p.prep), nullptr, nullptr, 0.f,
-                      slab.data_ptr<float>(), nullptr, nullptr, T, GM_SLAB);
-        launch_reduce_prep(s, y.data_ptr<float>(), slab.data_ptr<float>(),
-                           ks, u16p(xo), sso.data_ptr<float>(), m.w.rows, T);
-    } else {
-        launch_gemm16(s, m.w, u16p(p.prep), nullptr, nullptr, 0.f,
-                      y.data_ptr<float>(), u16p(xo), sso.data_ptr<float>(),
-                      T, GM_RES_SQ);
-    }
+    auto sso = torch::zeros({sumsq_numel(T)}, f32);
+    torch::Tensor slab;
+    if (split) slab = torch::zeros({slab_numel(m.w.rows / 16)}, f32);
+    launch_gemm16_residual(s, m.w, u16p(p.prep), y.data_ptr<float>(),
+                           u16p(xo), sso.data_ptr<float>(), T,
+                           split ? slab.data_ptr<float>() : nullptr,
+                           split ? 1 : 0);
     return {y, xo, sso, (int64_t)p.jtw};
 }
 
 // logits [T, rows] = mat . rmsnorm(x) * norm_w: launch_prep_x +
-// GM_NORM_PLAIN, T <= 64
+// launch_lmhead, T <= 64
 torch::Tensor gemm_lmhead(py::tuple mat, torch::Tensor x,
                           torch::Tensor norm_w, double eps,
                           int64_t dead_fill) {
@@ -1021,14 +965,14 @@ torch::Tensor gemm_lmhead(py::tuple mat, torch::Tensor x,
     auto lg = torch::zeros(
         {T, m.w.rows},
         torch::TensorOptions().device(torch::kCUDA).dtype(torch::kFloat32));
-    launch_gemm16(s, m.w, u16p(p.prep), u16p(normprep),
+    launch_lmhead(s, m.w, u16p(p.prep), u16p(normprep),
                   p.ss.data_ptr<float>(), (float)eps, lg.data_ptr<float>(),
-                  nullptr, nullptr, T, GM_NORM_PLAIN);
+                  T);
     return lg;
 }
 
 // gprep = f16(silu(m1 . n) * (m3 . n)), n = rmsnorm(x) * norm_w, in the
-// side-channel layout: launch_ffn16 (T <= 64) / launch_ffn16_mt.
+// side-channel layout: launch_ffn16.
 // -> (gprep i16 flat, jtw)
 std::tuple<torch::Tensor, int64_t> ffn_gate(py::tuple m1, py::tuple m3,
                                             torch::Tensor x,
@@ -1045,19 +989,15 @@ std::tuple<torch::Tensor, int64_t> ffn_gate(py::tuple m1, py::tuple m3,
     hipStream_t s = c10::hip::getCurrentHIPStream().stream();
     Panel p = stage_panel(s, x, a.w.cols, T, fill);
     auto g = zero_side(a.w.rows, p.jtw);
-    if (T > kMaxTokens)
-        launch_ffn16_mt(s, a.w, c.w, u16p(p.prep), u16p(normprep),
-                        p.ss.data_ptr<float>(), (float)eps, u16p(g), T);
-    else
-        launch_ffn16(s, a.w, c.w, u16p(p.prep), u16p(normprep),
-                     p.ss.data_ptr<float>(), (float)eps, u16p(g), T);
+    launch_ffn16(s, a.w, c.w, u16p(p.prep), u16p(normprep),
+                 p.ss.data_ptr<float>(), (float)eps, u16p(g), T);
     return {g, (int64_t)p.jtw};
 }
 
 // q [T, E] = rope(mq . n); rows pos[t] of slot seq[t] of k_store / v_store
 // get rope(mk . n) / mv . n in place. launch_qkv16 with a slab and
 // skip_finish = 0 (T <= 64: slab route + k_qkv_finish, or a fused route,
-// as qkv16_route decides) / launch_qkv16_mt.
+// as qkv16_route decides; T > 64: large-M, the slab unused).
 torch::Tensor qkv_project(py::tuple mq, py::tuple mk, py::tuple mv,
                           torch::Tensor x, torch::Tensor norm_w, double eps,
                           torch::Tensor k_store, torch::Tensor v_store,
@@ -1100,23 +1040,13 @@ torch::Tensor qkv_project(py::tuple mq, py::tuple mk, py::tuple mv,
     hipStream_t s = c10::hip::getCurrentHIPStream().stream();
     Panel p = stage_panel(s, x, E, T, fill);
     auto qb = torch::zeros({T, E}, f32);
-    if (T > kMaxTokens) {
-        launch_qkv16_mt(s, q.w, k.w, v.w, u16p(p.prep), u16p(normprep),
-                        p.ss.data_ptr<float>(), (float)eps,
-                        qb.data_ptr<float>(), h16(k_store), h16(v_store),
-                        pos.data_ptr<int>(), seq.data_ptr<int>(),
-                        inv_freq.data_ptr<float>(), E, d.Ekv, d.D, d.ctx, T);
-    } else {
-        TORCH_CHECK(qkv16_ks(E, d.Ekv) <= 8, "split factor out of range");
-        auto slab = torch::zeros(
-            {(int64_t)((E + 2 * d.Ekv) / 16) * 8 * kMaxTokens * 16}, f32);
-        launch_qkv16(s, q.w, k.w, v.w, u16p(p.prep), u16p(normprep),
-                     p.ss.data_ptr<float>(), (float)eps,
-                     qb.data_ptr<float>(), h16(k_store), h16(v_store),
-                     pos.data_ptr<int>(), seq.data_ptr<int>(),
-                     inv_freq.data_ptr<float>(), E, d.Ekv, d.D, d.ctx, T,
-                     slab.data_ptr<float>(), /*skip_finish=*/0);
-    }
+    TORCH_CHECK(qkv16_ks(E, d.Ekv) <= kMaxSplit, "split factor out of range");
+    auto slab = torch::zeros({slab_numel((E + 2 * d.Ekv) / 16)}, f32);
+    launch_qkv16(s, q.w, k.w, v.w, u16p(p.prep), u16p(normprep),
+                 p.ss.data_ptr<float>(), (float)eps, qb.data_ptr<float>(),
+                 h16(k_store), h16(v_store), pos.data_ptr<int>(),
+                 seq.data_ptr<int>(), inv_freq.data_ptr<float>(), E, d.Ekv,
+                 d.D, d.ctx, T, slab.data_ptr<float>(), /*skip_finish=*/0);
     return qb;
 }
 
@@ -1148,6 +1078,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gemm16_mt_rt", [](int64_t rows, int64_t T) {
         return (int64_t)gemm16_mt_rt((int)rows, (int)T);
     }, py::arg("rows"), py::arg("T"));
+    m.def("gemm16_res_route", [](int64_t rows, int64_t T, bool split_ok) {
+        return (int64_t)gemm16_res_route((int)rows, (int)T,
+                                         split_ok ? 1 : 0);
+    }, py::arg("rows"), py::arg("T"), py::arg("split_ok"));
     m.def("qkv16_route", [](int64_t E, int64_t Ekv, int64_t T,
                             bool has_slab) {
         return (int64_t)qkv16_route((int)E, (int)Ekv, (int)T,

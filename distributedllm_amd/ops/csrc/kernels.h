@@ -37,45 +37,47 @@ struct WMat2 {
     int wtype;  // WType (W_F32 never appears here — legacy path)
 };
 
-// k_gemm16 modes: fused residual + sumsq + xprep epilogue; input RMSNorm +
-// plain store (lm_head); split-K partials into slabs (follow with
-// launch_reduce_prep). The values are template arguments of the kernels —
-// keep them stable. (0 and 3 were a plain store and an atomic split-K.)
-enum GemmMode { GM_RES_SQ = 1, GM_NORM_PLAIN = 2, GM_SLAB = 4 };
+// ------------------------------------------------ MFMA layer launchers
+// One launcher per layer op, every T. Decode (T <= 64) runs the 1/2/4
+// column-tile kernels; large-M (T > 64: prefill and wide decode) covers all
+// T tokens in one launch on an XCD-aware (row-tile x 64-token-group) grid:
+// k_qkv16<…, true>, k_ffn16<…, true>, k_gemm16_mt. Side channels use the
+// jt_width(T) token-panel stride.
+int jt_width(int T);
 
-// split-K factor used by GM_SLAB (shared with the reducer)
-int gemm16_ks(int rows);
-
-// Route selectors: which instantiation each launcher below runs, as plain
-// host functions of the matrix and token counts (exported to the tests).
-//   gemm16_plain_rt  lm_head GM_NORM_PLAIN: row tiles per wave, 1 | 2 | 4
-//   ffn16_rt         launch_ffn16 (T <= 64) / launch_ffn16_mt: 1 | 2
-//   gemm16_mt_rt     launch_gemm16_mt: 1 | 2
-//   qkv16_route      launch_qkv16 (T <= 64): 0 slab split-K (RT=2),
-//                    1 fused RT=1, 2 fused RT=2
-//   qkv16_mt_rt      launch_qkv16_mt: 1 | 2
+// Route selectors: which instantiation each launcher runs, as plain host
+// functions of the matrix and token counts (exported to the tests). No
+// launcher branches on anything else.
+//   gemm16_plain_rt   launch_lmhead: row tiles per wave, 1 | 2 | 4
+//   ffn16_rt          launch_ffn16: 1 | 2
+//   gemm16_res_route  launch_gemm16_residual: 0 slab split-K (RT=2) +
+//                     reduce/prep pass (T <= 64, split_ok, rows/16 even),
+//                     1 fused residual epilogue (T <= 64 otherwise),
+//                     2 large-M k_gemm16_mt (T > 64)
+//   gemm16_mt_rt      route 2 of the above: 1 | 2
+//   qkv16_route       launch_qkv16 (T <= 64): 0 slab split-K (RT=2),
+//                     1 fused RT=1, 2 fused RT=2
+//   qkv16_mt_rt       launch_qkv16 (T > 64): 1 | 2
 int gemm16_plain_rt(int rows);
 int ffn16_rt(int rows, int T);
+int gemm16_res_route(int rows, int T, int split_ok);
 int gemm16_mt_rt(int rows, int T);
 int qkv16_route(int E, int Ekv, int T, int has_slab);
 int qkv16_mt_rt(int E, int Ekv, int T);
 
-// y[t] += sum of ks slab partials, then sumsq + f16 xprep of the result
-void launch_reduce_prep(hipStream_t s, float* y, const float* slab, int ks,
-                        unsigned short* xprep, float* ss, int cols, int T);
+// split-K factors of the slab routes: wo / w2 (shared with the reducer) and
+// qkv (shared with the fused-attention consumer)
+int gemm16_ks(int rows);
+int qkv16_ks(int E, int Ekv);
 
+// x [T, cols] -> f16 xprep panel of width jtw + sumsq (ss zeroed upstream)
 void launch_prep_x(hipStream_t s, const float* x, unsigned short* xprep,
-                   float* ss, int cols, int T);
+                   float* ss, int cols, int T, int jtw);
 
-void launch_gemm16(hipStream_t s, const WMat2& w,
-                   const unsigned short* bprep,
-                   const unsigned short* normprep, const float* ss_in,
-                   float eps, float* y, unsigned short* xprep_out,
-                   float* ss_out, int T, int mode);
-
-// slab != nullptr enables the RT=2 + split-K slab path for small models;
-// returns 1 when the slab path ran. skip_finish=1 leaves the slabs un-
-// combined for a fused-attention consumer (decode only).
+// T <= 64: slab != nullptr enables the RT=2 + split-K slab path for small
+// models; returns 1 when the slab path ran. skip_finish=1 leaves the slabs
+// un-combined for a fused-attention consumer (decode only). T > 64 ignores
+// slab and skip_finish and returns 0.
 int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
                  const WMat2& wv, const unsigned short* xprep,
                  const unsigned short* normprep, const float* ss_in,
@@ -84,13 +86,24 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
                  const float* inv_freq, int E, int Ekv, int D, int n_ctx,
                  int T, float* slab, int skip_finish);
 
-// the qkv slab split factor (shared with the fused-attention consumer)
-int qkv16_ks(int E, int Ekv);
-
 void launch_ffn16(hipStream_t s, const WMat2& w1, const WMat2& w3,
                   const unsigned short* xprep,
                   const unsigned short* normprep, const float* ss_in,
                   float eps, unsigned short* gprep, int T);
+
+// wo / w2: y += w . b, then sumsq of y into ss_out and f16(y) into
+// xprep_out. slab (rows/16 * gemm16_ks(rows) * 64 * 16 floats) is touched
+// by route 0 only; split_ok = 0 needs none.
+void launch_gemm16_residual(hipStream_t s, const WMat2& w,
+                            const unsigned short* bprep, float* y,
+                            unsigned short* xprep_out, float* ss_out, int T,
+                            float* slab, int split_ok);
+
+// lm_head, T <= 64: y = w . rmsnorm(b), plain f32 store
+void launch_lmhead(hipStream_t s, const WMat2& w,
+                   const unsigned short* bprep,
+                   const unsigned short* normprep, const float* ss_in,
+                   float eps, float* y, int T);
 
 void launch_rmsnorm(hipStream_t s, const float* x, const float* w, float* y,
                     int T, int E, float eps);
@@ -148,19 +161,17 @@ void launch_logprobs(hipStream_t s, const float* logits, const int* rows,
 // Log-probability of targets[t] under the lm_head applied to row t of a
 // [T, E] activation block, plus the row's arg-max, without ever forming
 // [T, V] logits. Three launches on one stream:
-//   launch_prep_x_score  launch_prep_x at the scoring panel width (whole
-//                        4-tile groups at every T); ss zeroed upstream,
-//                        ss must hold T rounded up to 64 floats
-//   launch_lmhead_score  k_lmhead_score: fused final norm + lm_head with a
+//   launch_prep_x        at the scoring panel width score_jt_width(T)
+//                        (whole 4-tile groups at every T); ss zeroed
+//                        upstream, ss must hold T rounded up to 64 floats
+//   launch_lmhead_score k_lmhead_score: fused final norm + lm_head with a
 //                        log-sum-exp epilogue -> P = V / (16 * RT) partials
 //                        per token, pkey/psum [T][P], and tgt_logit [T]
 //   launch_score_finish  k_score_finish: lp[t], top_id[t], top_lp[t]
 // A target outside [0, V) gives lp = NaN; top_id / top_lp are still
 // written. RT = lmhead_score_rt(V, T).
 int lmhead_score_rt(int V, int T);
-
-void launch_prep_x_score(hipStream_t s, const float* x,
-                         unsigned short* xprep, float* ss, int cols, int T);
+int score_jt_width(int T);
 
 void launch_lmhead_score(hipStream_t s, const WMat2& w,
                          const unsigned short* bprep,
@@ -174,14 +185,7 @@ void launch_score_finish(hipStream_t s, const unsigned long long* pkey,
                          const int* targets, float* lp, int* top_id,
                          float* top_lp, int T, int P, int V);
 
-// ---------------------------------------------------------- prefill path
-// Large-M (T > 64) layer launchers: one launch covers all T tokens with an
-// XCD-aware (row-tile x 64-token-group) grid. Side channels use the
-// jt_width(T) token-panel stride. qkv and ffn run the decode templates
-// with the large-M flag, k_qkv16<…, true> and k_ffn16<…, true>; wo / w2
-// run k_gemm16_mt.
-int jt_width(int T);
-
+// ---------------------------------------------------- prefill attention
 // Q-tiled (16 queries/block) matrix-core flash attention for prefill: each
 // K/V row is read once per 16 queries; mixed-seq tiles segment internally.
 // Requires D <= 128 (checked by the SliceEngine constructor).
@@ -191,21 +195,3 @@ void launch_attn_prefill(hipStream_t s, const float* q_buf,
                          unsigned short* out_prep, const int* pos,
                          const int* seq, int T, int H, int E, int Ekv,
                          int D, int n_ctx);
-
-void launch_qkv16_mt(hipStream_t s, const WMat2& wq, const WMat2& wk,
-                     const WMat2& wv, const unsigned short* xprep,
-                     const unsigned short* normprep, const float* ss_in,
-                     float eps, float* q_buf, __half* k_cache_layer,
-                     __half* v_cache_layer, const int* pos, const int* seq,
-                     const float* inv_freq, int E, int Ekv, int D,
-                     int n_ctx, int T);
-
-// wo / w2: y += w * b with the fused residual + sumsq + xprep epilogue
-void launch_gemm16_mt(hipStream_t s, const WMat2& w,
-                      const unsigned short* bprep, float* y,
-                      unsigned short* xprep_out, float* ss_out, int T);
-
-void launch_ffn16_mt(hipStream_t s, const WMat2& w1, const WMat2& w3,
-                     const unsigned short* xprep,
-                     const unsigned short* normprep, const float* ss_in,
-                     float eps, unsigned short* gprep, int T);

@@ -1,10 +1,12 @@
 // MFMA dequant-GEMM family of the slice engine (gfx950) — the production
 // path for every quantized / f16 layer, decode (T <= 64) and large-M
 // prefill / wide decode (T > 64: `k_qkv16<…, true>`, `k_ffn16<…, true>`,
-// `k_gemm16_mt`, behind the launch_*_mt launchers), plus the lm_head of
-// prompt scoring at any T (`k_lmhead_score`: large-M grid, log-sum-exp
-// epilogue, no logits). Design notes with the measurements that drove
-// each choice: docs/kernels.md.
+// `k_gemm16_mt`), plus the lm_head of prompt scoring at any T
+// (`k_lmhead_score`: large-M grid, log-sum-exp epilogue, no logits). One
+// launcher per layer op covers every T (launch_qkv16, launch_ffn16,
+// launch_gemm16_residual); the route selectors above them pick the kernel.
+// Design notes with the measurements that drove each choice:
+// docs/kernels.md.
 //
 // Matrix cores do the FLOPs; the VALU only unpacks. One
 // `mfma_f32_16x16x32_f16` consumes one 32-weight K-block of a 16-row tile.
@@ -25,8 +27,9 @@
 // A decode layer is 7-9 launches depending on model size: qkv (fused, or
 // RT=2 slab split-K whose finish is either k_qkv_finish or the attention
 // prologue), attention, wo (slab split-K + k_reduce_prep, or the fused
-// GM_RES_SQ epilogue when E/16 is odd), ffn gate (w1/w3 + SwiGLU), w2
-// (like wo). A prefill layer is 5: large-M qkv, attention, wo, ffn, w2.
+// GM_RES_SQ epilogue when E/16 is odd: gemm16_res_route), ffn gate (w1/w3
+// + SwiGLU), w2 (like wo). A prefill layer is 5: large-M qkv, attention,
+// wo, ffn, w2.
 //
 // Weight layout in HBM (repacked at load; python side in
 // engine/repack.py::repack_mfma), R = rows/16 row tiles:
@@ -58,6 +61,11 @@
 #include "device_common.h"
 #include "kernels.h"
 #include "logprobs_key.h"
+
+// k_gemm16 modes (described at the kernel). The values are template
+// arguments — keep them stable. (0 and 3 were a plain store and an atomic
+// split-K.)
+enum GemmMode { GM_RES_SQ = 1, GM_NORM_PLAIN = 2, GM_SLAB = 4 };
 
 // write-through 16 B store (sc0 sc1): the split-K slab publish leaves no
 // dirty lines in the writer XCD's L2, so the consumer kernel's reads are
@@ -1168,17 +1176,22 @@ int jt_width(int T) {
 
 // ------------------------------------------------- MFMA-path launchers
 
-void launch_prep_x(hipStream_t s, const float* x, unsigned short* xprep,
-                   float* ss, int cols, int T) {
-    // chunk columns so the launch spreads over ~256 CUs even at T=16
-    // (a T-block launch measured 4.6 us on 16 CUs); ss zeroed upstream
-    // ~128 blocks total: a microbenchmark of this kernel shape (see
-    // profiles/microbench_small_kernel.hip) shows larger grids LOSE —
-    // launch/ramp overhead outweighs the parallelism for ~1 MB of work
+// (T, chunks) grid of k_prep_x / k_reduce_prep: chunk columns so the
+// launch spreads over ~256 CUs even at T=16 (a T-block launch measured
+// 4.6 us on 16 CUs). ~128 blocks total: a microbenchmark of this kernel
+// shape (see profiles/microbench_small_kernel.hip) shows larger grids
+// LOSE — launch/ramp overhead outweighs the parallelism for ~1 MB of work
+static inline dim3 prep_grid(int cols, int T) {
     const int want = (128 + T - 1) / max(T, 1);
-    const int chunks = max(1, min(want, (cols >> 3) / 64));
-    hipLaunchKernelGGL(k_prep_x, dim3(T, chunks), dim3(BLOCK), 0, s, x,
-                       xprep, ss, cols, jt_width(T));
+    return dim3(T, max(1, min(want, (cols >> 3) / 64)));
+}
+
+// jtw: jt_width(T) for the layer path and the lm_head, score_jt_width(T)
+// for prompt scoring; ss zeroed upstream
+void launch_prep_x(hipStream_t s, const float* x, unsigned short* xprep,
+                   float* ss, int cols, int T, int jtw) {
+    hipLaunchKernelGGL(k_prep_x, prep_grid(cols, T), dim3(BLOCK), 0, s, x,
+                       xprep, ss, cols, jtw);
 }
 
 #define DISPATCH_JT(JTV, ...)            \
@@ -1228,6 +1241,25 @@ void launch_prep_x(hipStream_t s, const float* x, unsigned short* xprep,
             break;                               \
         }                                        \
     }
+
+// Row tiles per wave: RT2 instantiates {1, 2}, RT4 {1, 2, 4} (lm_head and
+// scoring only). Each case is a set of kernels — add none without a route
+// selector that returns it.
+#define DISPATCH_RT2(RTV, ...)       \
+    if ((RTV) == 2) {                \
+        constexpr int RTc = 2;       \
+        __VA_ARGS__;                 \
+    } else {                         \
+        constexpr int RTc = 1;       \
+        __VA_ARGS__;                 \
+    }
+
+#define DISPATCH_RT4(RTV, ...)       \
+    if ((RTV) == 4) {                \
+        constexpr int RTc = 4;       \
+        __VA_ARGS__;                 \
+    } else                           \
+        DISPATCH_RT2(RTV, __VA_ARGS__)
 
 // RT=2 (two row tiles per wave share one B panel: half the panel re-reads
 // and norm-build VALU per MFMA) is taken when the tile count is even and
@@ -1279,6 +1311,18 @@ int gemm16_mt_rt(int rows, int T) {
     return rt2_fills(rows >> 4, (T + 63) >> 6) ? 2 : 1;
 }
 
+// wo / w2 (launch_gemm16_residual). The tile count rows/16 alone underfills
+// 256 CUs in decode, so: 0 = split K across grid.y into plain-stored slabs
+// at RT=2 (needs an even tile count), then one reduce + residual + sumsq +
+// xprep pass (no atomics; the kernel boundary provides slab visibility) —
+// wins at every model size tested; 1 = unsplit fused GM_RES_SQ; 2 = large-M
+// k_gemm16_mt (T > 64), RT from gemm16_mt_rt. split_ok = the caller has a
+// slab and did not disable the split.
+int gemm16_res_route(int rows, int T, int split_ok) {
+    if (T > 64) return 2;
+    return (split_ok && (rows / 16) % 2 == 0) ? 0 : 1;
+}
+
 // RT=2 needs an even tile count in each of the three matrices
 static inline bool qkv_rt2_ok(int E, int Ekv) {
     return ((E >> 4) % 2 == 0) && ((Ekv >> 4) % 2 == 0);
@@ -1303,65 +1347,12 @@ int qkv16_mt_rt(int E, int Ekv, int T) {
     return (qkv_rt2_ok(E, Ekv) && rt2_fills(tiles3, (T + 63) >> 6)) ? 2 : 1;
 }
 
-void launch_reduce_prep(hipStream_t s, float* y, const float* slab, int ks,
-                        unsigned short* xprep, float* ss, int cols, int T) {
-    const int want = (128 + T - 1) / max(T, 1);  // see microbench note
-    const int chunks = max(1, min(want, (cols >> 3) / 64));
-    hipLaunchKernelGGL(k_reduce_prep, dim3(T, chunks), dim3(BLOCK), 0, s, y,
-                       slab, ks, xprep, ss, cols, pick_jt(T));
-}
-
-void launch_gemm16(hipStream_t s, const WMat2& w,
-                   const unsigned short* bprep,
-                   const unsigned short* normprep, const float* ss_in,
-                   float eps, float* y, unsigned short* xprep_out,
-                   float* ss_out, int T, int mode) {
-    const int R = w.rows / 16;
-    if (mode == GM_SLAB) {
-        // split K so R*KS lands near 2-3 blocks/CU (256 CUs)
-        const int ks = gemm16_ks(w.rows);
-        if (R % 2 == 0) {  // RT=2: halve the B-panel re-read
-            const dim3 grid(R / 2, ks);
-            DISPATCH_WT2(w.wtype, DISPATCH_JT(pick_jt(T),
-                hipLaunchKernelGGL(
-                    (k_gemm16<WTc, GM_SLAB, JTc, 2>), grid, dim3(BLOCK), 0,
-                    s, w, bprep, normprep, ss_in, eps, y, xprep_out, ss_out,
-                    T)));
-        } else {
-            const dim3 grid(R, ks);
-            DISPATCH_WT2(w.wtype, DISPATCH_JT(pick_jt(T),
-                hipLaunchKernelGGL(
-                    (k_gemm16<WTc, GM_SLAB, JTc>), grid, dim3(BLOCK), 0, s,
-                    w, bprep, normprep, ss_in, eps, y, xprep_out, ss_out,
-                    T)));
-        }
-        return;
-    }
-    const dim3 grid(R);
-    DISPATCH_WT2(w.wtype, DISPATCH_JT(pick_jt(T), {
-        if (mode == GM_RES_SQ)
-            hipLaunchKernelGGL((k_gemm16<WTc, GM_RES_SQ, JTc>), grid,
-                               dim3(BLOCK), 0, s, w, bprep, normprep, ss_in,
-                               eps, y, xprep_out, ss_out, T);
-        else {  // GM_NORM_PLAIN
-            const int rt = gemm16_plain_rt(w.rows);
-            if (rt == 4)
-                hipLaunchKernelGGL((k_gemm16<WTc, GM_NORM_PLAIN, JTc, 4>),
-                                   dim3(R / 4), dim3(BLOCK), 0, s, w, bprep,
-                                   normprep, ss_in, eps, y, xprep_out,
-                                   ss_out, T);
-            else if (rt == 2)
-                hipLaunchKernelGGL((k_gemm16<WTc, GM_NORM_PLAIN, JTc, 2>),
-                                   dim3(R / 2), dim3(BLOCK), 0, s, w, bprep,
-                                   normprep, ss_in, eps, y, xprep_out,
-                                   ss_out, T);
-            else
-                hipLaunchKernelGGL((k_gemm16<WTc, GM_NORM_PLAIN, JTc>), grid,
-                                   dim3(BLOCK), 0, s, w, bprep, normprep,
-                                   ss_in, eps, y, xprep_out, ss_out, T);
-        }
-    }));
-}
+// ------------------------------------------------------------ launchers
+// One per layer op, every T. Each branch below is taken on a selector's
+// value; T > 64 (the line gemm16_res_route and jt_width also draw) picks
+// between a selector's decode and large-M kernels: large-M covers all T
+// tokens in one launch on the XCD-aware (row tile x 64-token group) grid,
+// side channels at the jt_width(T) panel stride.
 
 int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
                  const WMat2& wv, const unsigned short* xprep,
@@ -1371,6 +1362,18 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
                  const float* inv_freq, int E, int Ekv, int D, int n_ctx,
                  int T, float* slab, int skip_finish) {
     const int tiles3 = (E + 2 * Ekv) >> 4;
+    if (T > 64) {
+        const int MT = (T + 63) >> 6;
+        const int jtw = jt_width(T);
+        DISPATCH_RT2(qkv16_mt_rt(E, Ekv, T), DISPATCH_WT2(wq.wtype,
+            hipLaunchKernelGGL(
+                (k_qkv16<WTc, 4, RTc, true>),
+                dim3(xcd_grid(tiles3 / RTc, MT)), dim3(BLOCK), 0, s, wq, wk,
+                wv, xprep, normprep, ss_in, eps, q_buf, k_cache_layer,
+                v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T, MT,
+                jtw)));
+        return 0;
+    }
     const int route = qkv16_route(E, Ekv, T, slab != nullptr);
     if (route == 0) {  // slab split-K + RT=2
         // RT=2 measured best (RT=4 loses ~3%: fill drops below 2/CU)
@@ -1389,124 +1392,97 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
         }
         return 1;
     }
-    if (route == 2) {
-        const dim3 grid(tiles3 / 2);
-        DISPATCH_WT2(wq.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
-            (k_qkv16<WTc, JTc, 2>), grid, dim3(BLOCK), 0, s, wq, wk, wv,
-            xprep, normprep, ss_in, eps, q_buf, k_cache_layer,
-            v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T, 0,
-            0)));
-        return 0;
-    }
-    const dim3 grid(tiles3);
-    DISPATCH_WT2(wq.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
-        (k_qkv16<WTc, JTc>), grid, dim3(BLOCK), 0, s, wq, wk, wv, xprep,
-        normprep, ss_in, eps, q_buf, k_cache_layer, v_cache_layer, pos, seq,
-        inv_freq, E, Ekv, D, n_ctx, T, 0, 0)));
+    // the fused routes 1 and 2 are named by their RT
+    DISPATCH_RT2(route, DISPATCH_WT2(wq.wtype, DISPATCH_JT(pick_jt(T),
+        hipLaunchKernelGGL(
+            (k_qkv16<WTc, JTc, RTc>), dim3(tiles3 / RTc), dim3(BLOCK), 0, s,
+            wq, wk, wv, xprep, normprep, ss_in, eps, q_buf, k_cache_layer,
+            v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T, 0, 0))));
     return 0;
 }
 
+// ffn stays fused at every T: a slab+finish variant measured slower at
+// every split/occupancy combination tried and was removed
 void launch_ffn16(hipStream_t s, const WMat2& w1, const WMat2& w3,
                   const unsigned short* xprep,
                   const unsigned short* normprep, const float* ss_in,
                   float eps, unsigned short* gprep, int T) {
     const int tilesF = w1.rows / 16;
-    if (ffn16_rt(w1.rows, T) == 2) {
-        const dim3 grid(tilesF / 2);
-        DISPATCH_WT2(w1.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
-            (k_ffn16<WTc, JTc, 2>), grid, dim3(BLOCK), 0, s, w1, w3, xprep,
-            normprep, ss_in, eps, gprep, T, 0, 0)));
+    const int rt = ffn16_rt(w1.rows, T);
+    if (T > 64) {
+        const int MT = (T + 63) >> 6;
+        const int jtw = jt_width(T);
+        DISPATCH_RT2(rt, DISPATCH_WT2(w1.wtype, hipLaunchKernelGGL(
+            (k_ffn16<WTc, 4, RTc, true>), dim3(xcd_grid(tilesF / RTc, MT)),
+            dim3(BLOCK), 0, s, w1, w3, xprep, normprep, ss_in, eps, gprep, T,
+            MT, jtw)));
         return;
     }
-
-    const dim3 grid(tilesF);
-    DISPATCH_WT2(w1.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
-        (k_ffn16<WTc, JTc>), grid, dim3(BLOCK), 0, s, w1, w3, xprep,
-        normprep, ss_in, eps, gprep, T, 0, 0)));
+    DISPATCH_RT2(rt, DISPATCH_WT2(w1.wtype, DISPATCH_JT(pick_jt(T),
+        hipLaunchKernelGGL(
+            (k_ffn16<WTc, JTc, RTc>), dim3(tilesF / RTc), dim3(BLOCK), 0, s,
+            w1, w3, xprep, normprep, ss_in, eps, gprep, T, 0, 0))));
 }
 
-void launch_qkv16_mt(hipStream_t s, const WMat2& wq, const WMat2& wk,
-                     const WMat2& wv, const unsigned short* xprep,
-                     const unsigned short* normprep, const float* ss_in,
-                     float eps, float* q_buf, __half* k_cache_layer,
-                     __half* v_cache_layer, const int* pos, const int* seq,
-                     const float* inv_freq, int E, int Ekv, int D,
-                     int n_ctx, int T) {
-    const int MT = (T + 63) >> 6;
-    const int jtw = jt_width(T);
-    const int tiles3 = (E + 2 * Ekv) >> 4;
-    if (qkv16_mt_rt(E, Ekv, T) == 2) {
-        const dim3 grid(xcd_grid(tiles3 / 2, MT));
-        DISPATCH_WT2(wq.wtype, hipLaunchKernelGGL(
-            (k_qkv16<WTc, 4, 2, true>), grid, dim3(BLOCK), 0, s, wq, wk, wv,
-            xprep, normprep, ss_in, eps, q_buf, k_cache_layer,
-            v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T, MT,
-            jtw));
-        return;
+void launch_gemm16_residual(hipStream_t s, const WMat2& w,
+                            const unsigned short* bprep, float* y,
+                            unsigned short* xprep_out, float* ss_out, int T,
+                            float* slab, int split_ok) {
+    const int R = w.rows / 16;
+    switch (gemm16_res_route(w.rows, T, split_ok)) {
+        case 0: {
+            // split K so R*KS lands near 2-3 blocks/CU (256 CUs); RT=2
+            // halves the B-panel re-read
+            const int ks = gemm16_ks(w.rows);
+            DISPATCH_WT2(w.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
+                (k_gemm16<WTc, GM_SLAB, JTc, 2>), dim3(R / 2, ks),
+                dim3(BLOCK), 0, s, w, bprep, nullptr, nullptr, 0.f, slab,
+                nullptr, nullptr, T)));
+            // y[t] += sum of the ks partials, then sumsq + xprep of y
+            hipLaunchKernelGGL(k_reduce_prep, prep_grid(w.rows, T),
+                               dim3(BLOCK), 0, s, y, slab, ks, xprep_out,
+                               ss_out, w.rows, pick_jt(T));
+            break;
+        }
+        case 1:
+            DISPATCH_WT2(w.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
+                (k_gemm16<WTc, GM_RES_SQ, JTc, 1>), dim3(R), dim3(BLOCK), 0,
+                s, w, bprep, nullptr, nullptr, 0.f, y, xprep_out, ss_out,
+                T)));
+            break;
+        default: {
+            const int MT = (T + 63) >> 6;
+            const int jtw = jt_width(T);
+            DISPATCH_RT2(gemm16_mt_rt(w.rows, T), DISPATCH_WT2(w.wtype,
+                hipLaunchKernelGGL(
+                    (k_gemm16_mt<WTc, 4, RTc>), dim3(xcd_grid(R / RTc, MT)),
+                    dim3(BLOCK), 0, s, w, bprep, y, xprep_out, ss_out, T, MT,
+                    jtw)));
+        }
     }
-    const dim3 grid(xcd_grid(tiles3, MT));
-    DISPATCH_WT2(wq.wtype, hipLaunchKernelGGL(
-        (k_qkv16<WTc, 4, 1, true>), grid, dim3(BLOCK), 0, s, wq, wk, wv, xprep,
-        normprep, ss_in, eps, q_buf, k_cache_layer, v_cache_layer, pos,
-        seq, inv_freq, E, Ekv, D, n_ctx, T, MT, jtw));
 }
 
-void launch_gemm16_mt(hipStream_t s, const WMat2& w,
-                      const unsigned short* bprep, float* y,
-                      unsigned short* xprep_out, float* ss_out, int T) {
-    const int MT = (T + 63) >> 6;
-    const int jtw = jt_width(T);
-    const int R = w.rows >> 4;
-    if (gemm16_mt_rt(w.rows, T) == 2) {
-        const dim3 grid(xcd_grid(R / 2, MT));
-        DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
-            (k_gemm16_mt<WTc, 4, 2>), grid, dim3(BLOCK), 0, s, w, bprep, y,
-            xprep_out, ss_out, T, MT, jtw));
-        return;
-    }
-    const dim3 grid(xcd_grid(R, MT));
-    DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
-        (k_gemm16_mt<WTc>), grid, dim3(BLOCK), 0, s, w, bprep, y, xprep_out,
-        ss_out, T, MT, jtw));
-}
-
-void launch_ffn16_mt(hipStream_t s, const WMat2& w1, const WMat2& w3,
-                     const unsigned short* xprep,
-                     const unsigned short* normprep, const float* ss_in,
-                     float eps, unsigned short* gprep, int T) {
-    const int MT = (T + 63) >> 6;
-    const int jtw = jt_width(T);
-    const int R = w1.rows >> 4;
-    if (ffn16_rt(w1.rows, T) == 2) {
-        const dim3 grid(xcd_grid(R / 2, MT));
-        DISPATCH_WT2(w1.wtype, hipLaunchKernelGGL(
-            (k_ffn16<WTc, 4, 2, true>), grid, dim3(BLOCK), 0, s, w1, w3,
-            xprep, normprep, ss_in, eps, gprep, T, MT, jtw));
-        return;
-    }
-    const dim3 grid(xcd_grid(R, MT));
-    DISPATCH_WT2(w1.wtype, hipLaunchKernelGGL(
-        (k_ffn16<WTc, 4, 1, true>), grid, dim3(BLOCK), 0, s, w1, w3, xprep, normprep,
-        ss_in, eps, gprep, T, MT, jtw));
+void launch_lmhead(hipStream_t s, const WMat2& w,
+                   const unsigned short* bprep,
+                   const unsigned short* normprep, const float* ss_in,
+                   float eps, float* y, int T) {
+    const int R = w.rows / 16;
+    const int rt = gemm16_plain_rt(w.rows);
+    DISPATCH_RT4(rt, DISPATCH_WT2(w.wtype, DISPATCH_JT(pick_jt(T),
+        hipLaunchKernelGGL(
+            (k_gemm16<WTc, GM_NORM_PLAIN, JTc, RTc>), dim3(R / RTc),
+            dim3(BLOCK), 0, s, w, bprep, normprep, ss_in, eps, y, nullptr,
+            nullptr, T))));
 }
 
 // ------------------------------------------------------ prompt scoring
 // token-panel stride of the scoring path: whole 4-tile groups at EVERY T
 // (k_lmhead_score is JT=4 only, so unlike jt_width it never packs 1 or 2)
-static inline int score_jtw(int T) {
+int score_jt_width(int T) {
     return (((T + 15) >> 4) + 3) & ~3;
 }
 
-void launch_prep_x_score(hipStream_t s, const float* x,
-                         unsigned short* xprep, float* ss, int cols,
-                         int T) {
-    const int want = (128 + T - 1) / max(T, 1);  // see launch_prep_x
-    const int chunks = max(1, min(want, (cols >> 3) / 64));
-    hipLaunchKernelGGL(k_prep_x, dim3(T, chunks), dim3(BLOCK), 0, s, x,
-                       xprep, ss, cols, score_jtw(T));
-}
-
-// Row tiles per wave of k_lmhead_score: the lm_head rule of launch_gemm16
+// Row tiles per wave of k_lmhead_score: the lm_head rule gemm16_plain_rt
 // (RT=4 from 448 blocks, RT=2 from 512) with the block count taken over
 // the MT token groups the way rt2_fills does for the other large-M kernels.
 int lmhead_score_rt(int V, int T) {
@@ -1524,25 +1500,11 @@ void launch_lmhead_score(hipStream_t s, const WMat2& w,
                          unsigned long long* pkey, float* psum,
                          float* tgt_logit, int T) {
     const int MT = (T + 63) >> 6;
-    const int jtw = score_jtw(T);
+    const int jtw = score_jt_width(T);
     const int R = w.rows >> 4;
-    switch (lmhead_score_rt(w.rows, T)) {
-        case 4:
-            DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
-                (k_lmhead_score<WTc, 4>), dim3(xcd_grid(R / 4, MT)),
-                dim3(BLOCK), 0, s, w, bprep, normprep, ss_in, eps, targets,
-                pkey, psum, tgt_logit, T, MT, jtw));
-            break;
-        case 2:
-            DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
-                (k_lmhead_score<WTc, 2>), dim3(xcd_grid(R / 2, MT)),
-                dim3(BLOCK), 0, s, w, bprep, normprep, ss_in, eps, targets,
-                pkey, psum, tgt_logit, T, MT, jtw));
-            break;
-        default:
-            DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
-                (k_lmhead_score<WTc, 1>), dim3(xcd_grid(R, MT)),
-                dim3(BLOCK), 0, s, w, bprep, normprep, ss_in, eps, targets,
-                pkey, psum, tgt_logit, T, MT, jtw));
-    }
+    const int rt = lmhead_score_rt(w.rows, T);
+    DISPATCH_RT4(rt, DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
+        (k_lmhead_score<WTc, RTc>), dim3(xcd_grid(R / RTc, MT)), dim3(BLOCK),
+        0, s, w, bprep, normprep, ss_in, eps, targets, pkey, psum, tgt_logit,
+        T, MT, jtw)));
 }

@@ -132,6 +132,13 @@ def gemm16_mt_rt(rows, T):
     return 2 if _rt2_fills(rows // 16, _mt(T)) else 1
 
 
+def gemm16_res_route(rows, T, split_ok):
+    """wo / w2: 0 slab split-K + reduce pass, 1 fused, 2 large-M."""
+    if T > 64:
+        return 2
+    return 0 if split_ok and rows // 16 % 2 == 0 else 1
+
+
 def _qkv_rt2_ok(E, Ekv):
     return (E >> 4) % 2 == 0 and (Ekv >> 4) % 2 == 0
 

@@ -143,6 +143,10 @@ def test_restated_host_functions_match_the_extension(core):
             assert core.ffn16_rt(r, T) == G.ffn16_rt(r, T)
             if T > 64:
                 assert core.gemm16_mt_rt(r, T) == G.gemm16_mt_rt(r, T)
+        for T in (1, 17, 64, 65, 128, 4096):
+            for ok in (False, True):
+                assert core.gemm16_res_route(r, T, ok) == \
+                    G.gemm16_res_route(r, T, ok)
     for E, Ekv in [(64, 64), (64, 32), (64, 16), (96, 48), (256, 64),
                    (672, 336), (1024, 1024), (4096, 1024), (5504, 5504),
                    (5472, 5472), (8192, 1024), (5120, 5120), (5136, 5136)]:
@@ -173,6 +177,13 @@ def test_every_route_variant_is_covered(core):
     # decode residual: GM_SLAB (rows/16 even), GM_RES_SQ at odd and even
     assert {(a[1] // 16 % 2, a[4]) for a in res if a[3] <= 64} == \
         {(1, False), (0, True), (0, False)}
+    # the residual hook passes split as split_ok; T > 64 cases have it off
+    assert {core.gemm16_res_route(a[1], a[3], a[4]) for a in res} == \
+        {0, 1, 2}
+    assert {a[1] // 16 % 2 for a in res if a[3] <= 64
+            and core.gemm16_res_route(a[1], a[3], a[4]) == 1} == {0, 1}
+    assert all(core.gemm16_res_route(a[1], a[3], False) == 1
+               for a in res if a[3] <= 64)
     assert {core.gemm16_ks(a[1]) for a in res if a[4]} == {8}
     wtypes = set(G.WTYPE.values())
     for cases, ti in ((res, 3), (ffn, 3), (qkv, 4)):
