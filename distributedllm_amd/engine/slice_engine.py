@@ -35,7 +35,8 @@ class HIPSliceEngine:
 
     def __init__(self, hp: ggml.Hparams, n_layers: int, first_layer: int,
                  n_ctx: int = 2048, max_batch: int = 16,
-                 max_prefill: Optional[int] = None):
+                 max_prefill: Optional[int] = None,
+                 gqa_attention: bool = True):
         from .. import ops
         core = ops.core()
         self.hp = hp
@@ -43,6 +44,9 @@ class HIPSliceEngine:
         self.n_layers = n_layers
         self.n_ctx = n_ctx
         self.max_batch = max_batch
+        # GQA models (2 <= n_head / n_head_kv <= 64): decode attention on
+        # the (token, KV head) matrix-core kernel; False keeps k_attention
+        self.gqa_attention = gqa_attention
         # prefill token cap per forward call (side channels scale with it;
         # larger prompts tile host-side in max_prefill chunks)
         if max_prefill is None:
@@ -51,7 +55,8 @@ class HIPSliceEngine:
             n_embd=hp.n_embd, n_head=hp.n_head, n_layers=n_layers,
             n_ff=hp.n_ff, n_ctx=n_ctx, max_batch=max_batch,
             eps=RMS_EPS, rope_base=ROPE_BASE, max_prefill=max_prefill,
-            n_head_kv=hp.kv_heads if hp.is_gqa else 0)
+            n_head_kv=hp.kv_heads if hp.is_gqa else 0,
+            gqa_attention=gqa_attention)
         self.device = "cuda"
         self.has_extra = False
         # weight-tensor references for clone_shared (filled by .random()
@@ -62,10 +67,12 @@ class HIPSliceEngine:
 
     @classmethod
     def from_ggml(cls, f: ggml.GGMLFile, n_ctx: int = 2048,
-                  max_batch: int = 16) -> "HIPSliceEngine":
+                  max_batch: int = 16,
+                  gqa_attention: bool = True) -> "HIPSliceEngine":
         hp = f.hparams
         first = hp.first_layer if hp.first_layer is not None else 0
-        eng = cls(hp, hp.n_layer, first, n_ctx, max_batch)
+        eng = cls(hp, hp.n_layer, first, n_ctx, max_batch,
+                  gqa_attention=gqa_attention)
         eng.load_layers(f)
         return eng
 
@@ -73,7 +80,8 @@ class HIPSliceEngine:
     def random(cls, hp: ggml.Hparams, n_layers: int, first_layer: int = 0,
                n_ctx: int = 2048, max_batch: int = 16, seed: int = 0,
                with_extra: bool = True,
-               max_prefill: Optional[int] = None) -> "HIPSliceEngine":
+               max_prefill: Optional[int] = None,
+               gqa_attention: bool = True) -> "HIPSliceEngine":
         """Random-init engine straight on the GPU (synthetic benchmarking).
 
         Generates weights directly in the repacked kernel layout — identical
@@ -81,7 +89,7 @@ class HIPSliceEngine:
         without materializing a multi-GB GGML file on disk.
         """
         eng = cls(hp, n_layers, first_layer, n_ctx, max_batch,
-                  max_prefill=max_prefill)
+                  max_prefill=max_prefill, gqa_attention=gqa_attention)
         g = torch.Generator(device="cuda")
         g.manual_seed(seed)
         E, F, V = hp.n_embd, hp.n_ff, hp.n_vocab
@@ -147,7 +155,8 @@ class HIPSliceEngine:
             "clone_shared requires an engine built by .random()/.from_ggml"
         twin = HIPSliceEngine(self.hp, self.n_layers, self.first_layer,
                               self.n_ctx, self.max_batch,
-                              max_prefill=int(self._eng.max_prefill))
+                              max_prefill=int(self._eng.max_prefill),
+                              gqa_attention=self.gqa_attention)
         for li, (an, fn, mats) in enumerate(self._layers_cache):
             twin._eng.set_layer(li, an, fn, mats)
         twin._layers_cache = self._layers_cache  # enables further clones

@@ -51,6 +51,11 @@ int64_t side_numel(int64_t cols, int64_t jtw) {
 // split-K partial slabs f32 [tiles][ks][64][16]; allocations take the
 // maximum split of 8
 constexpr int64_t kMaxSplit = 8;
+// split-KV partials of launch_attn_gqa: f32 [64][H][S][D + 2]
+int64_t gqa_ws_numel(int64_t H, int64_t D, int64_t n_ctx) {
+    return (int64_t)kMaxTokens * H * attn_gqa_splits((int)n_ctx, 1) * (D + 2);
+}
+
 int64_t slab_numel(int64_t tiles, int64_t ks = kMaxSplit) {
     return tiles * ks * kMaxTokens * 16;
 }
@@ -173,7 +178,7 @@ class SliceEngine {
     SliceEngine(int64_t n_embd, int64_t n_head, int64_t n_layers,
                 int64_t n_ff, int64_t n_ctx, int64_t max_batch, double eps,
                 double rope_base, int64_t max_prefill = 1024,
-                int64_t n_head_kv = 0)
+                int64_t n_head_kv = 0, bool gqa_attention = true)
         : E_((int)n_embd),
           H_((int)n_head),
           D_((int)(n_embd / n_head)),
@@ -181,7 +186,8 @@ class SliceEngine {
           L_((int)n_layers),
           ctx_((int)n_ctx),
           B_((int)max_batch),
-          eps_((float)eps) {
+          eps_((float)eps),
+          gqa_attention_(gqa_attention) {
         TORCH_CHECK(E_ % H_ == 0, "n_embd not divisible by n_head");
         TORCH_CHECK(D_ % 2 == 0, "head_dim must be even for RoPE pairs");
         TORCH_CHECK(D_ <= 128, "head_dim > 128 unsupported (the "
@@ -239,6 +245,9 @@ class SliceEngine {
         // (3E/16 tiles), ffn (2F/16), wo/w2 (E/16)
         slab_ = torch::zeros({slab_numel(std::max<int64_t>(
             {3 * (E_ / 16), 2 * (F_ / 16), E_ / 16}))}, f32);
+        // split-KV partials of the GQA decode attention
+        if (attn_route(H_, HK_, 1, 1, gqa_attention_) == 2)
+            gqa_ws_ = torch::zeros({gqa_ws_numel(H_, D_, ctx_)}, f32);
     }
 
     void set_layer(int64_t li, torch::Tensor attn_norm,
@@ -380,21 +389,30 @@ class SliceEngine {
                     hipGetErrorString(e));
         };
         float* slab = slab_.data_ptr<float>();
+        const int route = attn_route(H_, HK_, T, decode ? 1 : 0,
+                                     gqa_attention_ ? 1 : 0);
         for (int li = 0; li < L_; ++li) {
             Layer& l = layers_[li];
             __half* kc = kbase + (size_t)li * layer_stride;
             __half* vc = vbase + (size_t)li * layer_stride;
+            // the GQA kernel has no fused prologue: k_qkv_finish runs
             const int slab_used = launch_qkv16(
                 s, l.mq.w, l.mk.w, l.mv.w, xprep, u16p(l.attn_normprep),
                 ssa + li * ssw_, eps_, qb, kc, vc, pp, sp, ifr, E_, EK_,
-                D_, ctx_, T, slab, /*skip_finish=*/decode ? 1 : 0);
+                D_, ctx_, T, slab,
+                /*skip_finish=*/(decode && route != 2) ? 1 : 0);
             ck("qkv", li);
             // 16-query tiles are spans for prefill; the distinct-sequence
             // decode shape streams per token at any T, fused with the
-            // un-combined qkv slabs when the slab route ran
-            if (T > kMaxTokens && !decode) {
+            // un-combined qkv slabs when the slab route ran; GQA models
+            // run every such call on the (token, KV head) MFMA kernel
+            if (route == 1) {
                 launch_attn_prefill(s, qb, kc, vc, ab, aprep, pp, sp, T, H_,
                                     E_, EK_, D_, ctx_);
+            } else if (route == 2) {
+                launch_attn_gqa(s, qb, kc, vc, ab, aprep, pp, sp, T, H_,
+                                HK_, E_, EK_, D_, ctx_,
+                                gqa_ws_.data_ptr<float>());
             } else {
                 const bool fuse = decode && slab_used;
                 launch_attention(s, qb, kc, vc, ab, aprep, pp, sp, T, H_,
@@ -646,13 +664,14 @@ class SliceEngine {
     int ssw_ = kMaxTokens;   // per-layer sumsq side-channel stride
     int V_ = 0;
     float eps_;
+    bool gqa_attention_;     // GQA models: route attention to k_attn_gqa
     std::vector<Layer> layers_;
     std::vector<bool> loaded_;
     torch::Tensor kv_store_k_, kv_store_v_;
     torch::Tensor k_cache_, v_cache_, inv_freq_;
     torch::Tensor xn_, qb_, ab_, ffb_;
     torch::Tensor xprep_, aprep_, gprep_, ss_attn_, ss_ffn_, ss_tmp_;
-    torch::Tensor argmax_keys_, slab_;
+    torch::Tensor argmax_keys_, slab_, gqa_ws_;
     // prompt scoring, allocated by the first score() call
     torch::Tensor ss_score_, score_key_, score_sum_, score_tgt_;
     bool has_extra_ = false;
@@ -775,6 +794,28 @@ AttnResult attention_decode(torch::Tensor q, torch::Tensor k_store,
                      std::get<0>(r).data_ptr<float>(), u16p(std::get<1>(r)),
                      pos.data_ptr<int>(), seq.data_ptr<int>(), d.T, d.H,
                      d.E, d.Ekv, d.D, d.ctx, nullptr, 0, nullptr);
+    return r;
+}
+
+// k_attn_gqa (+ k_attn_gqa_merge); the split-KV workspace is per call
+AttnResult attention_decode_gqa(torch::Tensor q, torch::Tensor k_store,
+                                torch::Tensor v_store, torch::Tensor pos,
+                                torch::Tensor seq, int64_t n_head,
+                                int64_t n_head_kv, int64_t n_ctx,
+                                int64_t n_slots) {
+    const AttnDims d = check_q_args(q, n_head, n_head_kv, n_ctx, n_slots,
+                                    k_store, v_store, pos, seq);
+    TORCH_CHECK(attn_route(d.H, d.Hkv, d.T, 1, 1) == 2,
+                "k_attn_gqa serves 2 <= n_head / n_head_kv <= 64");
+    AttnResult r = alloc_attn_result(d);
+    auto ws = torch::zeros(
+        {gqa_ws_numel(d.H, d.D, d.ctx)},
+        torch::TensorOptions().device(torch::kCUDA).dtype(torch::kFloat32));
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    launch_attn_gqa(s, q.data_ptr<float>(), h16c(k_store), h16c(v_store),
+                    std::get<0>(r).data_ptr<float>(), u16p(std::get<1>(r)),
+                    pos.data_ptr<int>(), seq.data_ptr<int>(), d.T, d.H,
+                    d.Hkv, d.E, d.Ekv, d.D, d.ctx, ws.data_ptr<float>());
     return r;
 }
 
@@ -1094,6 +1135,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("k_store"), py::arg("v_store"), py::arg("pos"),
           py::arg("seq"), py::arg("n_head"), py::arg("n_head_kv"),
           py::arg("n_ctx"), py::arg("n_slots"));
+    m.def("attention_decode_gqa", &attention_decode_gqa, py::arg("q"),
+          py::arg("k_store"), py::arg("v_store"), py::arg("pos"),
+          py::arg("seq"), py::arg("n_head"), py::arg("n_head_kv"),
+          py::arg("n_ctx"), py::arg("n_slots"));
+    m.def("attn_gqa_chunk", [](int64_t n_ctx) {
+        return (int64_t)attn_gqa_chunk((int)n_ctx);
+    }, py::arg("n_ctx"));
+    m.def("attn_gqa_splits", [](int64_t n_ctx, int64_t T) {
+        return (int64_t)attn_gqa_splits((int)n_ctx, (int)T);
+    }, py::arg("n_ctx"), py::arg("T"));
+    m.def("attn_route", [](int64_t H, int64_t Hkv, int64_t T, bool decode,
+                           bool gqa_attention) {
+        return (int64_t)attn_route((int)H, (int)Hkv, (int)T, decode ? 1 : 0,
+                                   gqa_attention ? 1 : 0);
+    }, py::arg("H"), py::arg("Hkv"), py::arg("T"), py::arg("decode"),
+       py::arg("gqa_attention"));
     m.def("attention_decode_fused", &attention_decode_fused,
           py::arg("slab"), py::arg("k_store"), py::arg("v_store"),
           py::arg("pos"), py::arg("seq"), py::arg("inv_freq"),
@@ -1114,11 +1171,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "MI355X-native layer-slice inference engine (CDNA4 HIP kernels)";
     py::class_<SliceEngine, std::shared_ptr<SliceEngine>>(m, "SliceEngine")
         .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                      double, double, int64_t, int64_t>(),
+                      double, double, int64_t, int64_t, bool>(),
              py::arg("n_embd"), py::arg("n_head"), py::arg("n_layers"),
              py::arg("n_ff"), py::arg("n_ctx"), py::arg("max_batch"),
              py::arg("eps"), py::arg("rope_base"),
-             py::arg("max_prefill") = 1024, py::arg("n_head_kv") = 0)
+             py::arg("max_prefill") = 1024, py::arg("n_head_kv") = 0,
+             py::arg("gqa_attention") = true)
         .def("set_layer", &SliceEngine::set_layer)
         .def("set_extra", &SliceEngine::set_extra)
         .def("forward", &SliceEngine::forward, py::arg("x"),

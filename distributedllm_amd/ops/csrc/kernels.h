@@ -125,6 +125,28 @@ void launch_attention(hipStream_t s, const float* q_buf,
                       int n_ctx, const float* qkv_slab, int ks,
                       const float* inv_freq);
 
+// ------------------------------------------------ GQA decode attention
+// Same semantics as launch_attention without the fused prologue, for
+// 2 <= H/Hkv <= 64: one block per (token, KV head, 16 query heads, KV chunk)
+// on the matrix cores, every K/V row read once per group. Long contexts are
+// cut into attn_gqa_splits chunks of attn_gqa_chunk rows whose partials
+// k_attn_gqa_merge combines in fixed order; both are functions of n_ctx
+// alone for T <= 64 (a token's bits do not depend on T or on the other
+// tokens), and T > 64 runs one split. ws: f32 [64][H][S][D + 2] with
+// S = attn_gqa_splits(n_ctx, 1); untouched when S = 1.
+//   attn_route   0 launch_attention, 1 launch_attn_prefill (T > 64 and not
+//                decode), 2 launch_attn_gqa
+int attn_gqa_chunk(int n_ctx);
+int attn_gqa_splits(int n_ctx, int T);
+int attn_route(int H, int Hkv, int T, int decode, int gqa_attention);
+
+void launch_attn_gqa(hipStream_t s, const float* q_buf,
+                     const __half* k_cache_layer,
+                     const __half* v_cache_layer, float* out,
+                     unsigned short* out_prep, const int* pos,
+                     const int* seq, int T, int H, int Hkv, int E, int Ekv,
+                     int D, int n_ctx, float* ws);
+
 void launch_gemv(hipStream_t s, const WMat& w, const float* x,
                  const float* res, float* y, int T);
 
