@@ -317,6 +317,8 @@ class BatchGenerateCommand(Command):
         p.add_argument("--top-k", type=int, default=0)
         p.add_argument("--top-p", type=float, default=1.0)
         p.add_argument("--seed", type=int, default=None)
+        p.add_argument("--shared-prefix-file", metavar="PATH",
+                       help=_SHARED_PREFIX_HELP)
         p.add_argument("--speculative", action="store_true",
                        help="prompt-lookup speculative decoding (greedy "
                             "only): multiple tokens per forward when "
@@ -346,9 +348,12 @@ class BatchGenerateCommand(Command):
         f = ggml.GGMLFile.load(args.model,
                                extended=ggml.sniff_extended(args.model))
         n_slots = min(len(prompts), args.slots or 64, 64)
-        eng = engine_for_slice(f, n_ctx=args.ctx, max_batch=n_slots)
+        # the shared prefix lives in one KV slot of its own
+        extra = 1 if args.shared_prefix_file else 0
+        eng = engine_for_slice(f, n_ctx=args.ctx, max_batch=n_slots + extra)
         eng.attach_extra(slicer.make_extra_layers(f))
         tok = Tokenizer(f.vocab)
+        prefix = _read_shared_prefix(args.shared_prefix_file, tok)
 
         if args.speculative:
             if not args.greedy:
@@ -370,9 +375,10 @@ class BatchGenerateCommand(Command):
             return 0
 
         spec = bool(args.speculative)
-        bat = ContinuousBatcher(eng, max_slots=n_slots,
+        bat = ContinuousBatcher(eng, max_slots=n_slots + extra,
                                 spec_ngram=3 if spec else 0,
-                                spec_k=8 if spec else 0)
+                                spec_k=8 if spec else 0,
+                                shared_prefix=prefix)
         reqs = []
         for text in prompts:
             sampler = None if args.greedy else \
@@ -394,6 +400,22 @@ class BatchGenerateCommand(Command):
               f"{total / max(dt, 1e-9):.1f} tok/s, {steps} decode steps]",
               file=sys.stderr)
         return 0
+
+
+_SHARED_PREFIX_HELP = (
+    "text file with a prompt prefix (a system prompt) that is tokenised "
+    "once and kept in ONE KV slot: requests whose prompt tokens start with "
+    "it prefill only their own suffix and read the prefix rows from that "
+    "slot (shared-prefix attention)")
+
+
+def _read_shared_prefix(path, tok):
+    """Token ids of the --shared-prefix-file text (encoded like a prompt,
+    BOS included), or None without the option."""
+    if not path:
+        return None
+    with open(path) as f:
+        return tok.encode(f.read(), bos=True)
 
 
 class ServeHttpCommand(Command):
@@ -429,6 +451,9 @@ class ServeHttpCommand(Command):
                             "per lane and step) instead of copying the "
                             "logits to the host; same tokens per seed up "
                             "to f32 rounding at a CDF boundary")
+        p.add_argument("--shared-prefix-file", metavar="PATH",
+                       help=_SHARED_PREFIX_HELP + "; takes one of --slots "
+                            "per lane")
         p.add_argument("--pipeline", action="store_true",
                        help="serve across torch.distributed pipeline "
                             "ranks (launch with torchrun, one rank per "
@@ -450,6 +475,10 @@ class ServeHttpCommand(Command):
         from ..serving import ContinuousBatcher, build_http_app
 
         if args.pipeline:
+            if args.shared_prefix_file:
+                print("--shared-prefix-file is single-engine only",
+                      file=sys.stderr)
+                return 2
             return self._pipeline_main(args)
         f = ggml.GGMLFile.load(args.model,
                                extended=ggml.sniff_extended(args.model))
@@ -473,7 +502,9 @@ class ServeHttpCommand(Command):
                                 prefill_chunk=args.prefill_chunk or None,
                                 spec_ngram=3 if args.speculate else 0,
                                 spec_k=args.speculate,
-                                device_sampling=args.device_sampling)
+                                device_sampling=args.device_sampling,
+                                shared_prefix=_read_shared_prefix(
+                                    args.shared_prefix_file, tok))
         app, worker = build_http_app(bat, tok)
         try:
             uvicorn.run(app, host=args.host, port=args.port,

@@ -199,9 +199,17 @@ class HIPSliceEngine:
         self.has_extra = True
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor,
-                seq: torch.Tensor, decode: bool = False) -> torch.Tensor:
+                seq: torch.Tensor, decode: bool = False,
+                prefix=None) -> torch.Tensor:
         """decode=True asserts every token is a distinct sequence
         (batched decode) — enables the qkv-slab + fused-attention path.
+
+        prefix=(pslot, P, pfx): shared-prefix attention. Token t attends
+        rows [0, pfx[t]) of KV slot `pslot` followed by rows
+        [pfx[t], pos[t]] of its own slot seq[t]; pfx is an i32 [T] device
+        tensor of 0 (no prefix) or P, and pos[t] >= pfx[t]. Runs
+        k_attn_prefix + k_attn_prefix_tail at every T (ops/csrc/
+        attention.hip); MFMA-path models only.
 
         T > 64 (prefill) runs the native large-M path: hand-written
         XCD-grouped dequant-GEMM kernels over all T tokens, the layer
@@ -213,6 +221,13 @@ class HIPSliceEngine:
         # the weight stream + dequant once for the whole batch)
         cap = self._eng.max_prefill if self._mfma_path() \
             else self._eng.max_tokens
+        if prefix is not None:
+            pslot, P, pfx = prefix
+            return torch.cat([self._eng.forward(
+                x[t0:t0 + cap].contiguous(), pos[t0:t0 + cap].contiguous(),
+                seq[t0:t0 + cap].contiguous(), decode=decode,
+                prefix=(int(pslot), int(P), pfx[t0:t0 + cap].contiguous()))
+                for t0 in range(0, T, cap)], dim=0)
         if T <= cap:
             return self._eng.forward(x, pos, seq, decode=decode)
         # token-tile larger inputs; KV order is preserved because tile
@@ -224,6 +239,11 @@ class HIPSliceEngine:
                 x[t0:t1].contiguous(), pos[t0:t1].contiguous(),
                 seq[t0:t1].contiguous(), decode=decode))
         return torch.cat(outs, dim=0)
+
+    @property
+    def prefill_cap(self) -> int:
+        """Tokens per native forward call (the constructor's max_prefill)."""
+        return int(self._eng.max_prefill)
 
     def _mfma_path(self) -> bool:
         if not self._layers_cache:
@@ -415,7 +435,11 @@ class TorchSliceEngine:
         self.has_extra = True
 
     def forward(self, x: torch.Tensor, pos: torch.Tensor,
-                seq: torch.Tensor, decode: bool = False) -> torch.Tensor:
+                seq: torch.Tensor, decode: bool = False,
+                prefix=None) -> torch.Tensor:
+        """prefix=(pslot, P, pfx) as in HIPSliceEngine.forward: the prefix
+        rows of slot pslot and the token's own rows from pfx[t] on are
+        gathered into one K/V for the unchanged attention below."""
         hp = self.hp
         T, E = x.shape
         h, d = hp.n_head, hp.head_dim
@@ -423,6 +447,15 @@ class TorchSliceEngine:
         kv_map = torch.arange(h) // (h // hkv)  # GQA head sharing
         pos_l = pos.tolist()
         seq_l = seq.tolist()
+        if prefix is not None:
+            pslot, P, pfx = prefix
+            pslot, P, pfx_l = int(pslot), int(P), pfx.tolist()
+            if not 0 <= pslot < self.max_batch:
+                raise ValueError("prefix slot outside [0, max_batch)")
+            if not 1 <= P < self.n_ctx:
+                raise ValueError("prefix length outside [1, n_ctx)")
+            if any(f not in (0, P) or p < f for f, p in zip(pfx_l, pos_l)):
+                raise ValueError("pfx must be 0 or P, and pos >= pfx")
         for li in range(self.n_layers):
             gi = li + self.first_layer
             pre = f"layers.{gi}."
@@ -437,8 +470,12 @@ class TorchSliceEngine:
                 kt = rope_interleaved(k[t:t + 1].view(1, hkv, d), p)[0]
                 self.k_cache[li, b, p] = kt
                 self.v_cache[li, b, p] = v[t].view(hkv, d)
-                keys = self.k_cache[li, b, :p + 1][:, kv_map]
-                vals = self.v_cache[li, b, :p + 1][:, kv_map]
+                keys = self.k_cache[li, b, :p + 1]
+                vals = self.v_cache[li, b, :p + 1]
+                if prefix is not None and pfx_l[t] > 0:
+                    keys = torch.cat([self.k_cache[li, pslot, :P], keys[P:]])
+                    vals = torch.cat([self.v_cache[li, pslot, :P], vals[P:]])
+                keys, vals = keys[:, kv_map], vals[:, kv_map]
                 att = torch.einsum("hd,jhd->hj", qt, keys) / math.sqrt(d)
                 prob = torch.softmax(att, dim=-1)
                 o[t] = torch.einsum("hj,jhd->hd", prob, vals).reshape(E)

@@ -2,8 +2,8 @@
 // online-softmax decode kernel `k_attention` (optionally fused with the qkv
 // split-K finish: slab sum + RoPE + KV append in its prologue) and the
 // matrix-core prefill flash kernel `k_attn_prefill_mfma`, and the GQA decode
-// kernel `k_attn_gqa` (+ `k_attn_gqa_merge`), with their
-// launchers. All cover head dims D <= 128 only; the SliceEngine
+// kernel `k_attn_gqa` (+ `k_attn_gqa_merge`), and shared-prefix attention
+// `k_attn_prefix` + `k_attn_prefix_tail`, with their launchers. All cover head dims D <= 128 only; the SliceEngine
 // constructor rejects anything larger, so there is no fallback kernel.
 //
 // Not to be changed casually: k_attention's streaming loop (load order,
@@ -895,7 +895,358 @@ GQA_FN __global__ void k_attn_gqa_merge(
     gqa_store_out(ostar / lstar, h * D + d, t, E, jtw, out, out_prep);
 }
 
+// ------------------------------------------ shared-prefix attention (MFMA)
+// Token t attends rows [0, pfx[t]) of slot `pslot` followed by rows
+// [pfx[t], pos[t]] of its own slot seq[t]; pfx[t] is 0 or the common prefix
+// length P. k_attn_prefix covers the prefix rows: the 16 tokens of a tile are
+// the 16 MFMA columns of one (tile, query head, prefix chunk) block, so every
+// prefix row is read once per 16 tokens. The streaming loop is k_attn_gqa's
+// (same helpers, same two-buffer prefetch, no barrier and no branch around a
+// load); what differs is the Q tile (16 tokens of one head instead of 16
+// heads of one token), the K/V base (the prefix slot) and the epilogue, which
+// always writes un-normalised partials (m, l, o[D]) to ws [T][H][S][D + 2].
+// Columns without a prefix (pfx = 0, or past T) stream with q = 0: their
+// arithmetic stays finite and is dropped, and the epilogue writes the empty
+// partial (m = -inf, l = 0, o = 0) for those with t < T. MFMA columns are
+// independent, so a token's partial does not depend on its tile mates or on
+// its column. k_attn_prefix_tail then streams the token's own rows in f32
+// (k_attention's per-wave form), folds the prefix partials in, normalises
+// and stores.
+constexpr int PFX_MIN_CHUNK = 256;  // prefix rows per split, lower bound (unmeasured)
+constexpr int PFX_MAX_SPLITS = 8;   // splits of a full context (unmeasured)
+
+int attn_prefix_chunk(int n_ctx) {
+    const int per = (n_ctx + PFX_MAX_SPLITS - 1) / PFX_MAX_SPLITS;
+    return std::max(PFX_MIN_CHUNK, (per + 63) & ~63);
+}
+
+int attn_prefix_splits(int n_ctx, int T) {
+    if (T > 64) return 1;  // more than 4 tiles per head fill the chip
+    const int chunk = attn_prefix_chunk(n_ctx);
+    return (n_ctx + chunk - 1) / chunk;
+}
+
+template <int DC>
+GQA_FN __global__ __launch_bounds__(BLOCK) void k_attn_prefix(
+    const float* __restrict__ q_buf, const __half* __restrict__ k_cache,
+    const __half* __restrict__ v_cache, const int* __restrict__ pfx,
+    float* __restrict__ ws, int pslot, int P, int T, int grp, int E, int Ekv,
+    int D, int n_ctx, int chunk) {
+    constexpr int NKC = DC > 1 ? DC / 2 : 1;
+    constexpr int QW = NKC * 32;        // staged q row, halves
+    const int cs = (int)blockIdx.z * chunk;
+    if (cs >= P) return;                // block-uniform: chunk past the prefix
+    const int ce = min(P, cs + chunk);
+    const int t0 = (int)blockIdx.x * 16;
+    const int h = blockIdx.y;
+    const int H = gridDim.y;
+    const int hk = h / grp;             // GQA kv head
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = __builtin_amdgcn_readfirstlane(tid / WAVE);  // scalar
+    const int lq = lane & 15;
+    const int lg = lane >> 4;
+    const float inv_sqrt_d = rsqrtf((float)D);
+    const size_t base = (size_t)pslot * n_ctx * Ekv + hk * D;
+    const __half* kb = k_cache + base;
+    const __half* vb = v_cache + base;
+
+    // LDS as in k_attn_gqa: V tiles + staged Q while streaming, the waves'
+    // O partials [w][col][OSTR] after it
+    constexpr int OSTR = DC * 16 + 4;
+    constexpr int VT_BYTES = NWAVES * 4 * GQA_VSTRIDE * (int)sizeof(uint2);
+    constexpr int Q_BYTES = 16 * (QW + 8) * (int)sizeof(_Float16);
+    constexpr int O_BYTES = NWAVES * 16 * OSTR * (int)sizeof(float);
+    constexpr int LDS_BYTES =
+        VT_BYTES + Q_BYTES > O_BYTES ? VT_BYTES + Q_BYTES : O_BYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
+    __shared__ float lds_m[NWAVES][16];
+    __shared__ float lds_l[NWAVES][16];
+    __shared__ int lds_act[16];         // column's token shares the prefix
+    uint2* vt = reinterpret_cast<uint2*>(lds_raw) + wid * 4 * GQA_VSTRIDE;
+    _Float16 (*lds_q)[QW + 8] =
+        reinterpret_cast<_Float16 (*)[QW + 8]>(lds_raw + VT_BYTES);
+    float* lds_o = reinterpret_cast<float*>(lds_raw);
+
+    if (tid < 16) {
+        const int tc = t0 + tid;
+        lds_act[tid] = (tc < T && pfx[tc < T ? tc : t0] > 0) ? 1 : 0;
+    }
+    gqa_block_sync();
+    int nact = 0;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) nact += lds_act[c];
+
+    if (nact > 0) {                     // block-uniform
+        // Q tile -> LDS as f16, prescaled by 1/sqrt(D); zero past D and in
+        // columns without a prefix (the factor does the masking)
+        {
+            const float* qt = q_buf + (size_t)h * D;
+#pragma unroll
+            for (int i = 0; i < 16 * QW / BLOCK; ++i) {
+                const int idx = tid + i * BLOCK;
+                const int col = idx / QW;
+                const int d = idx % QW;
+                const bool ok = lds_act[col] != 0 && d < D;
+                const float v =
+                    qt[ok ? (size_t)(t0 + col) * E + d : (size_t)t0 * E] *
+                    (ok ? inv_sqrt_d : 0.0f);
+                lds_q[col][d] = (_Float16)v;
+            }
+        }
+        gqa_block_sync();
+        // score-MFMA B fragments: lane (column lq, k-span lg*8 of chunk c)
+        ABFrag qf[NKC];
+#pragma unroll
+        for (int c = 0; c < NKC; ++c) {
+            const uint4 u =
+                *reinterpret_cast<const uint4*>(&lds_q[lq][c * 32 + lg * 8]);
+            qf[c].u[0] = u.x; qf[c].u[1] = u.y;
+            qf[c].u[2] = u.z; qf[c].u[3] = u.w;
+        }
+
+        float m = -INFINITY, l = 0.0f;  // running state of column lq
+        f32x4 oacc[DC];
+#pragma unroll
+        for (int dc = 0; dc < DC; ++dc) oacc[dc] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+        // wave w streams tiles w, w+4, ... of the chunk, two per iteration
+        // (k_attn_gqa's loop: loads one tile ahead, a last tile wholly past
+        // the chunk reads row 0 and is masked)
+        int tj = cs + wid * 16;
+        if (tj < ce) {                  // wave-uniform, scalar
+            GqaTile<NKC> cur, alt;
+            gqa_load_tile(cur, kb, vb, tj, ce, Ekv, D, lq, lg);
+            do {
+                gqa_load_tile(alt, kb, vb, tj + NWAVES * 16, ce, Ekv, D, lq,
+                              lg);
+                gqa_tile_step<DC, NKC>(cur, qf, vt, tj, ce, lane, m, l, oacc);
+                gqa_load_tile(cur, kb, vb, tj + 2 * NWAVES * 16, ce, Ekv, D,
+                              lq, lg);
+                gqa_tile_step<DC, NKC>(alt, qf, vt, tj + NWAVES * 16, ce,
+                                       lane, m, l, oacc);
+                tj += 2 * NWAVES * 16;
+            } while (tj < ce);
+        }
+        gqa_block_sync();               // V tiles and Q are dead: reuse LDS
+
+        if (lg == 0) {
+            lds_m[wid][lq] = m;
+            lds_l[wid][lq] = l;
+        }
+#pragma unroll
+        for (int dc = 0; dc < DC; ++dc) {
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+                lds_o[(wid * 16 + lq) * OSTR + dc * 16 + lg * 4 + jj] =
+                    oacc[dc][jj];
+        }
+        gqa_block_sync();
+    }
+
+    // thread (col, d mod 16) writes the column's partial: the 4 waves merged
+    // in wave order, or the empty partial
+    const int col = tid >> 4;
+    const int tc = t0 + col;
+    if (tc >= T) return;
+    float* part = ws + (((size_t)tc * H + h) * gridDim.z + blockIdx.z) *
+                           (size_t)(D + 2);
+    if (lds_act[col] == 0) {
+        if ((tid & 15) == 0) {
+            part[0] = -INFINITY;
+            part[1] = 0.0f;
+        }
+        for (int d = tid & 15; d < D; d += 16) part[2 + d] = 0.0f;
+        return;
+    }
+    float mstar = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) mstar = fmaxf(mstar, lds_m[w][col]);
+    float wsc[NWAVES], lstar = 0.0f;
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) {
+        const float mw = lds_m[w][col];         // -inf: wave had no tile
+        wsc[w] = (mw == -INFINITY) ? 0.0f : __expf(mw - mstar);
+        lstar += lds_l[w][col] * wsc[w];
+    }
+    if ((tid & 15) == 0) {
+        part[0] = mstar;
+        part[1] = lstar;
+    }
+    for (int d = tid & 15; d < D; d += 16) {
+        float ostar = 0.0f;
+#pragma unroll
+        for (int w = 0; w < NWAVES; ++w)
+            ostar += lds_o[(w * 16 + col) * OSTR + d] * wsc[w];
+        part[2 + d] = ostar;
+    }
+}
+
+// 8 halves at `p` as floats, one unconditional 16-byte load (load_voct's
+// contract: whatever lies past D is finite and dropped by the caller)
+GQA_FN __device__ __forceinline__ void pfx_load8(const __half* __restrict__ p,
+                                                 float f[8]) {
+    const uint4 u = *reinterpret_cast<const uint4*>(p);
+    ABFrag a;
+    a.u[0] = u.x; a.u[1] = u.y; a.u[2] = u.z; a.u[3] = u.w;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = (float)a.v[e];
+}
+
+// One block per (token, head): rows [r0, pos[t]] of the token's own slot in
+// f32 with r0 = P where pfx[t] > 0, else 0 (k_attention's streaming loop:
+// wave w owns 4-row groups g = w mod 4, lane (sub, oct) one row's d-octet,
+// two groups per iteration), then one merge of the ceil(P/chunk) prefix
+// partials in ascending chunk order and of the 4 waves' partials in wave
+// order. The own span holds at least row pos[t], so the sum is never empty.
+GQA_FN __global__ __launch_bounds__(BLOCK) void k_attn_prefix_tail(
+    const float* __restrict__ q_buf, const __half* __restrict__ k_cache,
+    const __half* __restrict__ v_cache, float* __restrict__ out,
+    unsigned short* __restrict__ out_prep, const int* __restrict__ pos,
+    const int* __restrict__ seq, const int* __restrict__ pfx,
+    const float* __restrict__ ws, int P, int grp, int E, int Ekv, int D,
+    int n_ctx, int jtw, int chunk, int S) {
+    const int t = blockIdx.x;
+    const int h = blockIdx.y;
+    const int H = gridDim.y;
+    const int hk = h / grp;
+    const int r0 = pfx[t] > 0 ? P : 0;
+    const int J = pos[t] + 1 - r0;      // own rows r0 + [0, J)
+    const size_t base =
+        ((size_t)seq[t] * n_ctx + r0) * Ekv + (size_t)hk * D;
+    const __half* kb = k_cache + base;
+    const __half* vb = v_cache + base;
+    const float inv_sqrt_d = rsqrtf((float)D);
+
+    __shared__ float lds_m[NWAVES];
+    __shared__ float lds_l[NWAVES];
+    __shared__ float lds_o[16][128];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = tid / WAVE;
+    const int sub = lane >> 4;          // row within the 4-row group
+    const int d0 = (lane & 15) * 8;     // d-octet within the row
+    const bool dok = d0 < D;
+    const int dl = dok ? d0 : 0;        // octets past D load octet 0, q = 0
+    float q8[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int d = d0 + e;
+        q8[e] = (d < D) ? q_buf[(size_t)t * E + h * D + d] * inv_sqrt_d
+                        : 0.0f;
+    }
+    float m = -INFINITY, l = 0.0f;
+    float o8[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o8[e] = 0.0f;
+
+    for (int g = wid; g * 4 < J; g += 2 * NWAVES) {
+        const int j1 = g * 4 + sub;
+        const int j2 = (g + NWAVES) * 4 + sub;
+        const bool ok1 = j1 < J;
+        const bool ok2 = j2 < J;
+        float f1[8], f2[8];
+        // masked rows read row 0 of the span: a valid address, dropped below
+        pfx_load8(kb + (size_t)(ok1 ? j1 : 0) * Ekv + dl, f1);
+        pfx_load8(kb + (size_t)(ok2 ? j2 : 0) * Ekv + dl, f2);
+        float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            s1 = fmaf(f1[e], q8[e], s1);
+            s2 = fmaf(f2[e], q8[e], s2);
+        }
+#pragma unroll
+        for (int sh = 1; sh <= 8; sh <<= 1) {
+            s1 += gqa_shfl_xor(s1, lane, sh);
+            s2 += gqa_shfl_xor(s2, lane, sh);
+        }
+        if (!ok1) s1 = -INFINITY;
+        if (!ok2) s2 = -INFINITY;
+        float gm = fmaxf(s1, s2);
+        gm = fmaxf(gm, gqa_shfl_xor(gm, lane, 16));
+        gm = fmaxf(gm, gqa_shfl_xor(gm, lane, 32));
+        // gm is finite: the group's first row is inside the span
+        const float m_new = fmaxf(m, gm);
+        const float alpha = __expf(m - m_new);      // 0 on the first group
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o8[e] *= alpha;
+        const float p1 = __expf(s1 - m_new);        // 0 for masked rows
+        const float p2 = __expf(s2 - m_new);
+        float psum = p1 + p2;
+        psum += gqa_shfl_xor(psum, lane, 16);
+        psum += gqa_shfl_xor(psum, lane, 32);
+        l = l * alpha + psum;
+        m = m_new;
+        pfx_load8(vb + (size_t)(ok1 ? j1 : 0) * Ekv + dl, f1);
+        pfx_load8(vb + (size_t)(ok2 ? j2 : 0) * Ekv + dl, f2);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            o8[e] = fmaf(p1, f1[e], o8[e]);
+            o8[e] = fmaf(p2, f2[e], o8[e]);
+        }
+    }
+
+    if (dok) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) lds_o[wid * 4 + sub][d0 + e] = o8[e];
+    }
+    if (lane == 0) {
+        lds_m[wid] = m;
+        lds_l[wid] = l;
+    }
+    gqa_block_sync();
+    const int d = tid;
+    if (d >= D) return;
+    const int n = r0 > 0 ? (P + chunk - 1) / chunk : 0;     // <= S
+    const float* part = ws + ((size_t)t * H + h) * S * (size_t)(D + 2);
+    float mstar = -INFINITY;
+    for (int i = 0; i < n; ++i)
+        mstar = fmaxf(mstar, part[(size_t)i * (D + 2)]);
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) mstar = fmaxf(mstar, lds_m[w]);
+    float lstar = 0.0f, num = 0.0f;
+    for (int i = 0; i < n; ++i) {
+        const float* pi = part + (size_t)i * (D + 2);
+        const float sc = (pi[0] == -INFINITY) ? 0.0f : __expf(pi[0] - mstar);
+        lstar += pi[1] * sc;
+        num += pi[2 + d] * sc;
+    }
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) {
+        const float mw = lds_m[w];              // -inf: wave had no group
+        const float sc = (mw == -INFINITY) ? 0.0f : __expf(mw - mstar);
+        lstar += lds_l[w] * sc;
+        num += sc * (lds_o[w * 4 + 0][d] + lds_o[w * 4 + 1][d] +
+                     lds_o[w * 4 + 2][d] + lds_o[w * 4 + 3][d]);
+    }
+    gqa_store_out(num / lstar, h * D + d, t, E, jtw, out, out_prep);
+}
+
 // ============================================================== launchers
+
+void launch_attn_prefix(hipStream_t s, const float* q_buf,
+                        const __half* k_cache_layer,
+                        const __half* v_cache_layer, float* out,
+                        unsigned short* out_prep, const int* pos,
+                        const int* seq, const int* pfx, int pslot, int P,
+                        int T, int H, int Hkv, int E, int Ekv, int D,
+                        int n_ctx, float* ws) {
+    const int grp = H / Hkv;
+    const int S = attn_prefix_splits(n_ctx, T);
+    // one split covers the whole prefix, whatever its length
+    const int chunk = (S == 1) ? std::max(n_ctx, PFX_MIN_CHUNK)
+                               : attn_prefix_chunk(n_ctx);
+    auto kern = D <= 16 ? k_attn_prefix<1> : D <= 32 ? k_attn_prefix<2>
+              : D <= 64 ? k_attn_prefix<4> : k_attn_prefix<8>;
+    hipLaunchKernelGGL(kern, dim3((T + 15) / 16, H, S), dim3(BLOCK), 0, s,
+                       q_buf, k_cache_layer, v_cache_layer, pfx, ws, pslot, P,
+                       T, grp, E, Ekv, D, n_ctx, chunk);
+    hipLaunchKernelGGL(k_attn_prefix_tail, dim3(T, H), dim3(BLOCK), 0, s,
+                       q_buf, k_cache_layer, v_cache_layer, out, out_prep,
+                       pos, seq, pfx, ws, P, grp, E, Ekv, D, n_ctx,
+                       jt_width(T), chunk, S);
+}
 
 void launch_attn_gqa(hipStream_t s, const float* q_buf,
                      const __half* k_cache_layer,

@@ -56,6 +56,14 @@ int64_t gqa_ws_numel(int64_t H, int64_t D, int64_t n_ctx) {
     return (int64_t)kMaxTokens * H * attn_gqa_splits((int)n_ctx, 1) * (D + 2);
 }
 
+// prefix partials of launch_attn_prefix: f32 [T][H][S][D + 2], T <= 64 at
+// S = attn_prefix_splits(n_ctx, 1) splits, larger T (up to max_t) at one
+int64_t prefix_ws_numel(int64_t H, int64_t D, int64_t n_ctx, int64_t max_t) {
+    return std::max<int64_t>(
+               (int64_t)kMaxTokens * attn_prefix_splits((int)n_ctx, 1),
+               max_t) * H * (D + 2);
+}
+
 int64_t slab_numel(int64_t tiles, int64_t ks = kMaxSplit) {
     return tiles * ks * kMaxTokens * 16;
 }
@@ -315,8 +323,14 @@ class SliceEngine {
     // x: [T, E] f32 (modified in place and returned), pos/seq: [T] i32.
     // decode=true asserts every token is a distinct sequence (batched
     // decode), enabling the qkv-slab + fused-attention path.
+    // prefix = (pslot, P, pfx i32 [T]): token t attends rows [0, pfx[t]) of
+    // slot pslot and rows [pfx[t], pos[t]] of its own; pfx[t] is 0 or P and
+    // pos[t] >= pfx[t] (the caller's contract, kernels.h). Every T then runs
+    // qkv with its finish pass and launch_attn_prefix instead of the routed
+    // attention kernel. None: nothing changes.
     torch::Tensor forward(torch::Tensor x, torch::Tensor pos,
-                          torch::Tensor seq, bool decode = false) {
+                          torch::Tensor seq, bool decode = false,
+                          py::object prefix = py::none()) {
         check_f32(x, "x");
         check_i32(pos, "pos");
         check_i32(seq, "seq");
@@ -356,6 +370,37 @@ class SliceEngine {
         float* qb = qb_.data_ptr<float>();
         float* ab = ab_.data_ptr<float>();
 
+        const bool shared = !prefix.is_none();
+        int pslot = 0, plen = 0;
+        const int* fp = nullptr;
+        torch::Tensor pfx;
+        if (shared) {
+            TORCH_CHECK(layers_[0].mfma,
+                        "the legacy f32 path does not support prefix");
+            auto tup = prefix.cast<py::tuple>();
+            TORCH_CHECK(tup.size() == 3, "prefix must be (pslot, P, pfx)");
+            const int64_t ps = tup[0].cast<int64_t>();
+            const int64_t pl = tup[1].cast<int64_t>();
+            pfx = tup[2].cast<torch::Tensor>();
+            TORCH_CHECK(ps >= 0 && ps < B_, "prefix slot ", ps,
+                        " outside [0, max_batch)");
+            TORCH_CHECK(pl >= 1 && pl < ctx_, "prefix length ", pl,
+                        " outside [1, n_ctx)");
+            check_i32(pfx, "pfx");
+            TORCH_CHECK(pfx.numel() == T, "pfx size");
+            if (bounds_check)
+                TORCH_CHECK(((pfx == 0) | ((pfx == pl) & (pos >= pfx)))
+                                .all().item<bool>(),
+                            "pfx must be 0 or P, and pos >= pfx");
+            pslot = (int)ps;
+            plen = (int)pl;
+            fp = pfx.data_ptr<int>();
+            if (!prefix_ws_.defined())  // first use
+                prefix_ws_ = torch::zeros(
+                    {prefix_ws_numel(H_, D_, ctx_, maxP_)},
+                    torch::TensorOptions().device(torch::kCUDA).dtype(
+                        torch::kFloat32));
+        }
         if (!layers_[0].mfma) {
             forward_legacy(s, xp, pp, sp, T, kbase, vbase, ifr, layer_stride);
             return x;
@@ -400,13 +445,17 @@ class SliceEngine {
                 s, l.mq.w, l.mk.w, l.mv.w, xprep, u16p(l.attn_normprep),
                 ssa + li * ssw_, eps_, qb, kc, vc, pp, sp, ifr, E_, EK_,
                 D_, ctx_, T, slab,
-                /*skip_finish=*/(decode && route != 2) ? 1 : 0);
+                /*skip_finish=*/(decode && route != 2 && !shared) ? 1 : 0);
             ck("qkv", li);
             // 16-query tiles are spans for prefill; the distinct-sequence
             // decode shape streams per token at any T, fused with the
             // un-combined qkv slabs when the slab route ran; GQA models
             // run every such call on the (token, KV head) MFMA kernel
-            if (route == 1) {
+            if (shared) {
+                launch_attn_prefix(s, qb, kc, vc, ab, aprep, pp, sp, fp,
+                                   pslot, plen, T, H_, HK_, E_, EK_, D_,
+                                   ctx_, prefix_ws_.data_ptr<float>());
+            } else if (route == 1) {
                 launch_attn_prefill(s, qb, kc, vc, ab, aprep, pp, sp, T, H_,
                                     E_, EK_, D_, ctx_);
             } else if (route == 2) {
@@ -672,6 +721,7 @@ class SliceEngine {
     torch::Tensor xn_, qb_, ab_, ffb_;
     torch::Tensor xprep_, aprep_, gprep_, ss_attn_, ss_ffn_, ss_tmp_;
     torch::Tensor argmax_keys_, slab_, gqa_ws_;
+    torch::Tensor prefix_ws_;  // allocated by the first forward with prefix
     // prompt scoring, allocated by the first score() call
     torch::Tensor ss_score_, score_key_, score_sum_, score_tgt_;
     bool has_extra_ = false;
@@ -816,6 +866,35 @@ AttnResult attention_decode_gqa(torch::Tensor q, torch::Tensor k_store,
                     std::get<0>(r).data_ptr<float>(), u16p(std::get<1>(r)),
                     pos.data_ptr<int>(), seq.data_ptr<int>(), d.T, d.H,
                     d.Hkv, d.E, d.Ekv, d.D, d.ctx, ws.data_ptr<float>());
+    return r;
+}
+
+// k_attn_prefix + k_attn_prefix_tail; the partials workspace is per call
+AttnResult attention_prefix(torch::Tensor q, torch::Tensor k_store,
+                            torch::Tensor v_store, torch::Tensor pos,
+                            torch::Tensor seq, torch::Tensor pfx,
+                            int64_t pslot, int64_t P, int64_t n_head,
+                            int64_t n_head_kv, int64_t n_ctx,
+                            int64_t n_slots) {
+    const AttnDims d = check_q_args(q, n_head, n_head_kv, n_ctx, n_slots,
+                                    k_store, v_store, pos, seq);
+    TORCH_CHECK(pslot >= 0 && pslot < n_slots,
+                "pslot out of [0, n_slots)");
+    TORCH_CHECK(P >= 1 && P < n_ctx, "P out of [1, n_ctx)");
+    check_i32(pfx, "pfx");
+    TORCH_CHECK(pfx.dim() == 1 && pfx.numel() == d.T, "pfx must be [T]");
+    TORCH_CHECK(((pfx == 0) | ((pfx == P) & (pos >= pfx))).all().item<bool>(),
+                "pfx must be 0 or P, and pos >= pfx");
+    AttnResult r = alloc_attn_result(d);
+    auto ws = torch::zeros(
+        {prefix_ws_numel(d.H, d.D, d.ctx, d.T)},
+        torch::TensorOptions().device(torch::kCUDA).dtype(torch::kFloat32));
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    launch_attn_prefix(s, q.data_ptr<float>(), h16c(k_store), h16c(v_store),
+                       std::get<0>(r).data_ptr<float>(), u16p(std::get<1>(r)),
+                       pos.data_ptr<int>(), seq.data_ptr<int>(),
+                       pfx.data_ptr<int>(), (int)pslot, (int)P, d.T, d.H,
+                       d.Hkv, d.E, d.Ekv, d.D, d.ctx, ws.data_ptr<float>());
     return r;
 }
 
@@ -1139,6 +1218,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("k_store"), py::arg("v_store"), py::arg("pos"),
           py::arg("seq"), py::arg("n_head"), py::arg("n_head_kv"),
           py::arg("n_ctx"), py::arg("n_slots"));
+    m.def("attention_prefix", &attention_prefix, py::arg("q"),
+          py::arg("k_store"), py::arg("v_store"), py::arg("pos"),
+          py::arg("seq"), py::arg("pfx"), py::arg("pslot"), py::arg("P"),
+          py::arg("n_head"), py::arg("n_head_kv"), py::arg("n_ctx"),
+          py::arg("n_slots"));
+    m.def("attn_prefix_chunk", [](int64_t n_ctx) {
+        return (int64_t)attn_prefix_chunk((int)n_ctx);
+    }, py::arg("n_ctx"));
+    m.def("attn_prefix_splits", [](int64_t n_ctx, int64_t T) {
+        return (int64_t)attn_prefix_splits((int)n_ctx, (int)T);
+    }, py::arg("n_ctx"), py::arg("T"));
     m.def("attn_gqa_chunk", [](int64_t n_ctx) {
         return (int64_t)attn_gqa_chunk((int)n_ctx);
     }, py::arg("n_ctx"));
@@ -1180,7 +1270,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def("set_layer", &SliceEngine::set_layer)
         .def("set_extra", &SliceEngine::set_extra)
         .def("forward", &SliceEngine::forward, py::arg("x"),
-             py::arg("pos"), py::arg("seq"), py::arg("decode") = false)
+             py::arg("pos"), py::arg("seq"), py::arg("decode") = false,
+             py::arg("prefix") = py::none())
         .def("embed", &SliceEngine::embed)
         .def("logits", &SliceEngine::logits, py::arg("x"),
              py::arg("all_logits") = false)

@@ -147,6 +147,32 @@ void launch_attn_gqa(hipStream_t s, const float* q_buf,
                      const int* seq, int T, int H, int Hkv, int E, int Ekv,
                      int D, int n_ctx, float* ws);
 
+// ------------------------------------------------ shared-prefix attention
+// Token t attends rows [0, pfx[t]) of slot `pslot`, then rows
+// [pfx[t], pos[t]] of slot seq[t]. pfx is a device i32 [T] whose entries are
+// 0 (plain attention over the token's own rows) or P; pos[t] >= pfx[t];
+// 0 <= pslot < slots and 1 <= P < n_ctx. Two launches on one stream, any T:
+//   k_attn_prefix       one block per (16-token tile, head, prefix chunk) on
+//                       the matrix cores, the tile's tokens as MFMA columns:
+//                       un-normalised partials ws [T][H][S][D + 2]
+//   k_attn_prefix_tail  one block per (token, head): the own rows in f32,
+//                       the prefix partials folded in ascending chunk order,
+//                       out and the f16 out_prep side channel
+// Chunking follows the GQA rule: attn_prefix_chunk rows per split and
+// S = attn_prefix_splits splits, functions of n_ctx alone for T <= 64 (a
+// token's bits do not depend on T, its tile mates or its column), S = 1 for
+// T > 64. ws holds T * H * S * (D + 2) floats.
+int attn_prefix_chunk(int n_ctx);
+int attn_prefix_splits(int n_ctx, int T);
+
+void launch_attn_prefix(hipStream_t s, const float* q_buf,
+                        const __half* k_cache_layer,
+                        const __half* v_cache_layer, float* out,
+                        unsigned short* out_prep, const int* pos,
+                        const int* seq, const int* pfx, int pslot, int P,
+                        int T, int H, int Hkv, int E, int Ekv, int D,
+                        int n_ctx, float* ws);
+
 void launch_gemv(hipStream_t s, const WMat& w, const float* x,
                  const float* res, float* y, int T);
 

@@ -23,6 +23,7 @@ device ids of argmax / sample, results in the same host sync as the ids.
 """
 from __future__ import annotations
 
+import inspect
 from collections import deque
 from contextlib import nullcontext as _nullctx
 from dataclasses import dataclass, field
@@ -47,6 +48,7 @@ class Request:
     _next_tok: int = -1   # token to feed at _pos on the next step
     _pos: int = -1
     _pf_pos: int = 0      # prompt tokens already prefilled (chunked)
+    _pfx: int = 0         # rows [0, _pfx) come from the shared-prefix slot
     # None = off; n >= 0: the chosen token's log-probability plus the n
     # most likely tokens, per generated token (index-aligned with `out`)
     logprobs: Optional[int] = None
@@ -74,7 +76,8 @@ class ContinuousBatcher:
                  eos_id: Optional[int] = None, engines=None,
                  prefill_chunk: Optional[int] = None,
                  spec_ngram: int = 0, spec_k: int = 0,
-                 device_sampling: bool = False):
+                 device_sampling: bool = False,
+                 shared_prefix: Optional[Sequence[int]] = None):
         """engines: optional list of k weight-sharing clones ("lanes");
         global slot s lives on lane s%k as that clone's local slot s//k,
         and on CUDA each lane's forward runs on its own HIP stream —
@@ -106,7 +109,25 @@ class ContinuousBatcher:
         copied to the host: a lane's sampled rows share one
         `engine.sample` call on the lane's stream, with the repetition
         state kept per lane-local slot on the device. Raises ValueError
-        if an engine has no `sample` (the pipeline facade)."""
+        if an engine has no `sample` (the pipeline facade).
+
+        shared_prefix: token ids of a prompt prefix (a system prompt) that
+        is kept ONCE per lane. Each lane reserves its last KV slot and
+        prefills the ids into it before its first admission, so requests
+        have one slot per lane less. A request whose prompt starts with the
+        ids, is longer than them and did not ask for echo prefills only
+        `prompt[P:-1]` at positions P onward, and all its rows (admission,
+        chunked prefill, decode, speculative drafts) go through
+        `forward(..., prefix=(slot, P, pfx))` with pfx = P: attention reads
+        rows [0, P) from the reserved slot (engine.forward). Every other
+        request carries pfx = 0 in the same forwards, and a forward none of
+        whose rows shares is called without `prefix`, exactly as before.
+        Rows [0, P) of a sharing request's own slot stay allocated and
+        unused: KV capacity is unchanged. Raises ValueError for an engine
+        whose forward takes no `prefix` (the pipeline facade), a prefix
+        that does not fit n_ctx or the engine's max_prefill (its
+        `prefill_cap`), or when no
+        slot would be left for requests."""
         self.engine = engine
         self.lanes = engines if engines else [engine]
         k = len(self.lanes)
@@ -115,6 +136,28 @@ class ContinuousBatcher:
         slots = per_lane * k
         if max_slots is not None:
             slots = min(slots, max_slots)
+        self._prefix: List[int] = list(map(int, shared_prefix or []))
+        self._prefix_slot = per_lane - 1    # lane-local
+        self._prefix_ready = False
+        if shared_prefix is not None:
+            P = len(self._prefix)
+            for e in self.lanes:
+                if "prefix" not in inspect.signature(e.forward).parameters:
+                    raise ValueError(
+                        "shared_prefix needs an engine whose forward takes "
+                        "prefix=")
+                n_ctx = getattr(e, "n_ctx", None)
+                if P < 1 or (n_ctx is not None and P >= n_ctx):
+                    raise ValueError(
+                        f"shared prefix of {P} tokens must be in [1, n_ctx)")
+                cap = getattr(e, "prefill_cap", None)
+                if cap is not None and P > cap:
+                    raise ValueError(
+                        f"shared prefix of {P} tokens exceeds the engine's "
+                        f"max_prefill={cap}")
+            slots -= k
+            if slots < 1:
+                raise ValueError("shared_prefix leaves no slot for requests")
         self.n_slots = max(1, slots)
         self.eos_id = eos_id
         self.free: List[int] = list(range(self.n_slots))
@@ -205,10 +248,37 @@ class ContinuousBatcher:
         self.queue.append(r)
         return r
 
+    def _forward(self, eng, toks, pos, seq, pfx, decode=False):
+        """One lane forward of the (token, pos, seq, pfx) rows on the
+        current stream; `prefix` only when some row shares."""
+        t = torch.tensor(toks, dtype=torch.int32, device=self._dev)
+        p = torch.tensor(pos, dtype=torch.int32, device=self._dev)
+        q = torch.tensor(seq, dtype=torch.int32, device=self._dev)
+        if not any(pfx):
+            return eng.forward(eng.embed(t), p, q, decode=decode)
+        f = torch.tensor(pfx, dtype=torch.int32, device=self._dev)
+        return eng.forward(eng.embed(t), p, q, decode=decode,
+                           prefix=(self._prefix_slot, len(self._prefix), f))
+
+    def _prefill_prefix(self) -> None:
+        """The shared prefix into every lane's reserved slot, on the lane's
+        stream (the lane's later forwards read these rows)."""
+        P = len(self._prefix)
+        for j, eng in enumerate(self.lanes):
+            ctx = (torch.cuda.stream(self._streams[j])
+                   if self._streams is not None else _nullctx())
+            with ctx:
+                self._forward(eng, self._prefix, list(range(P)),
+                              [self._prefix_slot] * P, [0] * P)
+        self._prefix_ready = True
+
     def _admit(self) -> List[Request]:
         """Returns the requests that finished during admission: pure
         scoring requests (echo, max_new == 0) whose prefill completed."""
         finished: List[Request] = []
+        P = len(self._prefix)
+        if P and not self._prefix_ready and self.queue:
+            self._prefill_prefix()
         eng = self.engine  # n_ctx/bounds source; lanes share hparams
         n_ctx = getattr(eng, "n_ctx", 1 << 30)
         k = len(self.lanes)
@@ -223,8 +293,11 @@ class ContinuousBatcher:
                 r.done = True
                 continue
             r.slot = self.free.pop()
-            r._pf_pos = 0
-            if len(r.prompt) > 1:
+            shares = (P > 0 and len(r.prompt) > P and not r.echo and
+                      r.prompt[:P] == self._prefix)
+            r._pfx = P if shares else 0
+            r._pf_pos = r._pfx
+            if len(r.prompt) - 1 > r._pf_pos:
                 self.prefilling[r.slot] = r
             else:
                 self._prefilled(r, finished)
@@ -242,7 +315,7 @@ class ContinuousBatcher:
             if not reqs:
                 continue
             budget = budget_full
-            toks, pos, seq = [], [], []
+            toks, pos, seq, pfx = [], [], [], []
             echo = []   # (request, first stream row, row count)
             for r in reqs:
                 end = len(r.prompt) - 1
@@ -257,6 +330,7 @@ class ContinuousBatcher:
                 toks += r.prompt[r._pf_pos:r._pf_pos + take]
                 pos += list(range(r._pf_pos, r._pf_pos + take))
                 seq += [r.slot // k] * take
+                pfx += [r._pfx] * take
                 r._pf_pos += take
             if not toks:
                 continue
@@ -267,13 +341,7 @@ class ContinuousBatcher:
             ctx = (torch.cuda.stream(self._streams[j])
                    if self._streams is not None else _nullctx())
             with ctx:
-                t = torch.tensor(toks, dtype=torch.int32,
-                                 device=self._dev)
-                p = torch.tensor(pos, dtype=torch.int32,
-                                 device=self._dev)
-                q = torch.tensor(seq, dtype=torch.int32,
-                                 device=self._dev)
-                y = lane_eng.forward(lane_eng.embed(t), p, q)
+                y = self._forward(lane_eng, toks, pos, seq, pfx)
                 if echo:
                     scored.append(self._score_lane(lane_eng, y, echo))
         if scored:
@@ -405,22 +473,18 @@ class ContinuousBatcher:
                     toks = [r._next_tok for r in reqs]
                     pos = [r._pos for r in reqs]
                     seq = [s // k for s in lane_slots]
+                    pfx = [r._pfx for r in reqs]
                     decode = True   # one row per request, distinct seqs
                 else:
-                    toks, pos, seq = [], [], []
+                    toks, pos, seq, pfx = [], [], [], []
                     for r, s_, d in zip(reqs, lane_slots, drafts):
                         toks += [r._next_tok] + d
                         pos += list(range(r._pos, r._pos + 1 + len(d)))
                         seq += [s_ // k] * (1 + len(d))
+                        pfx += [r._pfx] * (1 + len(d))
                     decode = False  # same-seq multi-pos rows (mixed
                     #                 admission stream semantics)
-                t = torch.tensor(toks, dtype=torch.int32,
-                                 device=self._dev)
-                p = torch.tensor(pos, dtype=torch.int32,
-                                 device=self._dev)
-                q = torch.tensor(seq, dtype=torch.int32,
-                                 device=self._dev)
-                y = eng.forward(eng.embed(t), p, q, decode=decode)
+                y = self._forward(eng, toks, pos, seq, pfx, decode)
                 lg = eng.logits(y, all_logits=True)
                 greedy_ids = None
                 if any(self._is_greedy(r) for r in reqs):

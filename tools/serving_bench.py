@@ -61,19 +61,35 @@ def main():
                     help="ask for per-token log-probabilities with this "
                          "many top alternatives (0..8) on every request "
                          "(default: off)")
+    ap.add_argument("--shared-prefix", type=int, default=0, metavar="N",
+                    help="every prompt is N common tokens followed by "
+                         "--prompt-len of its own, and the batcher keeps "
+                         "the N tokens once (shared_prefix=); also prints "
+                         "the admission and the decode step times")
+    ap.add_argument("--no-prefix-sharing", action="store_true",
+                    help="with --shared-prefix: the same prompts, but the "
+                         "batcher is not told (every request prefills and "
+                         "attends its own copy) - the baseline of the "
+                         "comparison")
     args = ap.parse_args()
     if args.device_sampling and args.temperature is None:
         ap.error("--device-sampling needs --temperature")
 
     hp = PRESETS[args.model].hparams(ggml.FTYPE_MOSTLY_Q4_0)
+    share = args.shared_prefix > 0 and not args.no_prefix_sharing
+    # sharing reserves one KV slot per lane: --slots stay usable
     eng = HIPSliceEngine.random(hp, n_layers=hp.n_layer, n_ctx=args.ctx,
-                                max_batch=args.slots, with_extra=True)
+                                max_batch=args.slots + (1 if share else 0),
+                                with_extra=True)
     lanes = None
     if args.lanes > 1:
         lanes = [eng] + [eng.clone_shared()
                          for _ in range(args.lanes - 1)]
     g = torch.Generator().manual_seed(1)
+    common = torch.randint(3, hp.n_vocab, (args.shared_prefix,),
+                           generator=g).tolist()
     bat = ContinuousBatcher(eng, engines=lanes,
+                            shared_prefix=common if share else None,
                             prefill_chunk=args.prefill_chunk or None,
                             spec_ngram=3 if args.speculate else 0,
                             spec_k=args.speculate,
@@ -89,7 +105,8 @@ def main():
                        seed=args.seed + n_sub[0] - 1, top_k=args.top_k,
                        top_p=args.top_p)
 
-    reqs = [bat.submit(torch.randint(3, hp.n_vocab, (args.prompt_len,),
+    reqs = [bat.submit(common +
+                       torch.randint(3, hp.n_vocab, (args.prompt_len,),
                                      generator=g).tolist(),
                        args.num_tokens, sampler=sampler(),
                        logprobs=args.logprobs)
@@ -100,9 +117,15 @@ def main():
     done_at = {}
     long_at = max(1, args.num_tokens // 4)
     stalls = []  # per-step wall time after the long arrivals
+    admit, decode = [], []  # step wall times with / without admission work
     while bat.pending:
         ts = time.perf_counter()
+        admitting = bool(bat.queue or bat.prefilling)
         fin = bat.step()
+        if args.shared_prefix:
+            torch.cuda.synchronize()
+            (admit if admitting else decode).append(
+                time.perf_counter() - ts)
         if fin:
             torch.cuda.synchronize()
             now = time.perf_counter() - t0
@@ -138,6 +161,13 @@ def main():
           f"{total} tokens in {dt:.2f}s = {total/dt:.0f} tok/s, "
           f"{steps} decode steps; completion p50={p(0.5):.2f}s "
           f"p95={p(0.95):.2f}s max={lat[-1]:.2f}s")
+    if args.shared_prefix:
+        dd = sorted(decode) or [float("nan")]
+        print(f"shared prefix {args.shared_prefix} tokens, sharing "
+              f"{'on' if share else 'off'}: {len(admit)} admitting steps "
+              f"(admission + one decode each) {sum(admit)*1e3:.1f} ms in "
+              f"all; decode-only steps p50={dd[len(dd)//2]*1e3:.2f} ms "
+              f"min={dd[0]*1e3:.2f} ms over {len(decode)} steps")
     if stalls:
         ss = sorted(stalls)
         print(f"per-step wall after long arrivals (stall = decode "
