@@ -80,6 +80,8 @@ class RunNodeCommand(Command):
         p.add_argument("--device", default=None,
                        help="force engine device (cuda/cpu); default auto")
         p.add_argument("--n-ctx", type=int, default=2048)
+        p.add_argument("--kv-dtype", choices=["f16", "q8"], default="f16",
+                       help=_KV_DTYPE_HELP)
         p.add_argument("--reverse", action="store_true",
                        help="dial out to a proxy instead of listening")
         p.add_argument("--proxy-host", default="127.0.0.1")
@@ -91,14 +93,15 @@ class RunNodeCommand(Command):
         if args.reverse:
             from ..cluster.proxy import connect_then_serve
             state = NodeState(args.uploads_dir, device=args.device,
-                              n_ctx=args.n_ctx)
+                              n_ctx=args.n_ctx, kv_dtype=args.kv_dtype)
             print(f"[node] reverse-connecting to "
                   f"{args.proxy_host}:{args.proxy_port}")
             connect_then_serve(args.proxy_host, args.proxy_port, state,
                                name=args.name)
             return 0
         run_server(args.host, args.port, args.uploads_dir,
-                   device=args.device, n_ctx=args.n_ctx)
+                   device=args.device, n_ctx=args.n_ctx,
+                   kv_dtype=args.kv_dtype)
         return 0
 
 
@@ -311,6 +314,8 @@ class BatchGenerateCommand(Command):
                        help="max concurrent requests (default: engine "
                             "max_batch)")
         p.add_argument("--ctx", type=int, default=2048)
+        p.add_argument("--kv-dtype", choices=["f16", "q8"], default="f16",
+                       help=_KV_DTYPE_HELP)
         p.add_argument("--temp", type=float, default=0.7)
         p.add_argument("--rp", type=float, default=1.1)
         p.add_argument("--greedy", action="store_true")
@@ -350,7 +355,8 @@ class BatchGenerateCommand(Command):
         n_slots = min(len(prompts), args.slots or 64, 64)
         # the shared prefix lives in one KV slot of its own
         extra = 1 if args.shared_prefix_file else 0
-        eng = engine_for_slice(f, n_ctx=args.ctx, max_batch=n_slots + extra)
+        eng = engine_for_slice(f, n_ctx=args.ctx, max_batch=n_slots + extra,
+                               kv_dtype=args.kv_dtype)
         eng.attach_extra(slicer.make_extra_layers(f))
         tok = Tokenizer(f.vocab)
         prefix = _read_shared_prefix(args.shared_prefix_file, tok)
@@ -408,6 +414,11 @@ _SHARED_PREFIX_HELP = (
     "it prefill only their own suffix and read the prefix rows from that "
     "slot (shared-prefix attention)")
 
+_KV_DTYPE_HELP = (
+    "KV cache element type: q8 stores int8 rows with one f16 scale per "
+    "(row, KV head): half the KV bytes of f16 (twice the slots or context "
+    "for the same HBM); not combinable with --shared-prefix-file")
+
 
 def _read_shared_prefix(path, tok):
     """Token ids of the --shared-prefix-file text (encoded like a prompt,
@@ -436,6 +447,8 @@ class ServeHttpCommand(Command):
                             "256 requests on 3B); 0 = auto lane fit "
                             "(the round-1 multi-stream mode)")
         p.add_argument("--ctx", type=int, default=2048)
+        p.add_argument("--kv-dtype", choices=["f16", "q8"], default="f16",
+                       help=_KV_DTYPE_HELP)
         p.add_argument("--prefill-chunk", type=int, default=64,
                        help="max prompt tokens prefilled per lane per "
                             "decode step (latency fairness; 0 = "
@@ -491,7 +504,8 @@ class ServeHttpCommand(Command):
                 w_bytes = sum(len(t.raw) for t in f.tensors) * 2.2
                 fit = max(1, int((260e9 - w_bytes) // max(kv, 1)))
                 n_lanes = min(5, fit) if fit >= 3 else 1
-        eng = engine_for_slice(f, n_ctx=args.ctx, max_batch=args.slots)
+        eng = engine_for_slice(f, n_ctx=args.ctx, max_batch=args.slots,
+                               kv_dtype=args.kv_dtype)
         eng.attach_extra(slicer.make_extra_layers(f))
         lanes = None
         if n_lanes > 1 and hasattr(eng, "clone_shared"):
@@ -548,7 +562,8 @@ class ServeHttpCommand(Command):
         sl = slicer.make_slice(f, first, first + count - 1) \
             if world > 1 else f
         ex = slicer.make_extra_layers(f)
-        eng = engine_for_slice(sl, n_ctx=args.ctx, max_batch=args.slots)
+        eng = engine_for_slice(sl, n_ctx=args.ctx, max_batch=args.slots,
+                               kv_dtype=args.kv_dtype)
         eng.attach_extra(ex)  # rank 0: embed; last rank: lm head
         if rank > 0:
             serve_forever(eng, rank, world)

@@ -55,11 +55,11 @@ class EngineSlice:
     """A loaded GGML slice running on the best local engine."""
 
     def __init__(self, path: str, n_ctx: int = 2048, max_batch: int = 16,
-                 device: Optional[str] = None):
+                 device: Optional[str] = None, kv_dtype: str = "f16"):
         from ..engine import engine_for_slice
         f = ggml.GGMLFile.load(path, extended=True)
         self.engine = engine_for_slice(f, n_ctx=n_ctx, max_batch=max_batch,
-                                       device=device)
+                                       device=device, kv_dtype=kv_dtype)
         self.name = os.path.basename(path)
         self.first_layer = f.hparams.first_layer or 0
         self.n_layers = f.hparams.n_layer
@@ -84,7 +84,7 @@ class EngineSlice:
 
 class NodeState:
     def __init__(self, uploads_dir: str, device: Optional[str] = None,
-                 n_ctx: int = 2048):
+                 n_ctx: int = 2048, kv_dtype: str = "f16"):
         self.lock = threading.Lock()
         # serializes forward passes: concurrent propagate_forward calls
         # would interleave KV-cache writes of the shared engine (the
@@ -94,6 +94,7 @@ class NodeState:
         self.slice = None  # DummySlice | EngineSlice
         self.device = device
         self.n_ctx = n_ctx
+        self.kv_dtype = kv_dtype
 
     # --------------------------------------------------------- handlers
 
@@ -148,7 +149,7 @@ class NodeState:
                 s = DummySlice(rec.path)
             else:
                 s = EngineSlice(rec.path, n_ctx=self.n_ctx,
-                                device=self.device)
+                                device=self.device, kv_dtype=self.kv_dtype)
         except Exception as e:  # noqa: BLE001
             return P.ResponseError(operation="load_slice",
                                    error="slice_load_error",
@@ -221,9 +222,11 @@ class NodeServer(socketserver.ThreadingTCPServer):
     daemon_threads = True
 
     def __init__(self, host: str, port: int, uploads_dir: str,
-                 device: Optional[str] = None, n_ctx: int = 2048):
+                 device: Optional[str] = None, n_ctx: int = 2048,
+                 kv_dtype: str = "f16"):
         super().__init__((host, port), _Handler)
-        self.node_state = NodeState(uploads_dir, device=device, n_ctx=n_ctx)
+        self.node_state = NodeState(uploads_dir, device=device, n_ctx=n_ctx,
+                                    kv_dtype=kv_dtype)
 
     @property
     def port(self) -> int:
@@ -231,7 +234,9 @@ class NodeServer(socketserver.ThreadingTCPServer):
 
 
 def run_server(host: str, port: int, uploads_dir: str,
-               device: Optional[str] = None, n_ctx: int = 2048) -> None:
-    srv = NodeServer(host, port, uploads_dir, device=device, n_ctx=n_ctx)
+               device: Optional[str] = None, n_ctx: int = 2048,
+               kv_dtype: str = "f16") -> None:
+    srv = NodeServer(host, port, uploads_dir, device=device, n_ctx=n_ctx,
+                     kv_dtype=kv_dtype)
     print(f"[node] serving on {host}:{srv.port}, uploads in {uploads_dir}")
     srv.serve_forever()

@@ -29,6 +29,28 @@ from .repack import (W_F32, _BYTE_GTYPES, _upload_mat, random_tiles,
                      repack_mfma)
 from .sampler import LOGPROBS_MAX_TOP
 
+KV_DTYPES = ("f16", "q8")
+
+
+def _check_kv_dtype(kv_dtype: str) -> str:
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, "
+                         f"got {kv_dtype!r}")
+    return kv_dtype
+
+
+def quantize_kv_rows(x: torch.Tensor) -> torch.Tensor:
+    """Fake-quantise K/V rows the way the q8 cache stores them (ops/csrc/
+    attention_kv8.hip), in f32: per head (last axis) s = f16(amax / 127),
+    q = clamp(rint(x / s), -127, 127), all q = 0 where s == 0; returns
+    s * q."""
+    x = x.to(torch.float32)
+    s = (x.abs().amax(dim=-1, keepdim=True) / 127.0).to(
+        torch.float16).to(torch.float32)
+    q = torch.where(s > 0, torch.round(x / torch.where(s > 0, s, 1.0)),
+                    torch.zeros_like(x)).clamp(-127.0, 127.0)
+    return s * q
+
 
 class HIPSliceEngine:
     """Production engine: CDNA4 kernels, weights resident in HBM3E."""
@@ -36,7 +58,7 @@ class HIPSliceEngine:
     def __init__(self, hp: ggml.Hparams, n_layers: int, first_layer: int,
                  n_ctx: int = 2048, max_batch: int = 16,
                  max_prefill: Optional[int] = None,
-                 gqa_attention: bool = True):
+                 gqa_attention: bool = True, kv_dtype: str = "f16"):
         from .. import ops
         core = ops.core()
         self.hp = hp
@@ -47,6 +69,9 @@ class HIPSliceEngine:
         # GQA models (2 <= n_head / n_head_kv <= 64): decode attention on
         # the (token, KV head) matrix-core kernel; False keeps k_attention
         self.gqa_attention = gqa_attention
+        # "q8": int8 KV cache with one f16 scale per (row, KV head): half
+        # the KV bytes, every attention call on k_attn_kv8; no prefix=
+        self.kv_dtype = _check_kv_dtype(kv_dtype)
         # prefill token cap per forward call (side channels scale with it;
         # larger prompts tile host-side in max_prefill chunks)
         if max_prefill is None:
@@ -56,7 +81,8 @@ class HIPSliceEngine:
             n_ff=hp.n_ff, n_ctx=n_ctx, max_batch=max_batch,
             eps=RMS_EPS, rope_base=ROPE_BASE, max_prefill=max_prefill,
             n_head_kv=hp.kv_heads if hp.is_gqa else 0,
-            gqa_attention=gqa_attention)
+            gqa_attention=gqa_attention,
+            kv_dtype=KV_DTYPES.index(kv_dtype))
         self.device = "cuda"
         self.has_extra = False
         # weight-tensor references for clone_shared (filled by .random()
@@ -67,12 +93,12 @@ class HIPSliceEngine:
 
     @classmethod
     def from_ggml(cls, f: ggml.GGMLFile, n_ctx: int = 2048,
-                  max_batch: int = 16,
-                  gqa_attention: bool = True) -> "HIPSliceEngine":
+                  max_batch: int = 16, gqa_attention: bool = True,
+                  kv_dtype: str = "f16") -> "HIPSliceEngine":
         hp = f.hparams
         first = hp.first_layer if hp.first_layer is not None else 0
         eng = cls(hp, hp.n_layer, first, n_ctx, max_batch,
-                  gqa_attention=gqa_attention)
+                  gqa_attention=gqa_attention, kv_dtype=kv_dtype)
         eng.load_layers(f)
         return eng
 
@@ -81,7 +107,8 @@ class HIPSliceEngine:
                n_ctx: int = 2048, max_batch: int = 16, seed: int = 0,
                with_extra: bool = True,
                max_prefill: Optional[int] = None,
-               gqa_attention: bool = True) -> "HIPSliceEngine":
+               gqa_attention: bool = True,
+               kv_dtype: str = "f16") -> "HIPSliceEngine":
         """Random-init engine straight on the GPU (synthetic benchmarking).
 
         Generates weights directly in the repacked kernel layout — identical
@@ -89,7 +116,8 @@ class HIPSliceEngine:
         without materializing a multi-GB GGML file on disk.
         """
         eng = cls(hp, n_layers, first_layer, n_ctx, max_batch,
-                  max_prefill=max_prefill, gqa_attention=gqa_attention)
+                  max_prefill=max_prefill, gqa_attention=gqa_attention,
+                  kv_dtype=kv_dtype)
         g = torch.Generator(device="cuda")
         g.manual_seed(seed)
         E, F, V = hp.n_embd, hp.n_ff, hp.n_vocab
@@ -156,7 +184,8 @@ class HIPSliceEngine:
         twin = HIPSliceEngine(self.hp, self.n_layers, self.first_layer,
                               self.n_ctx, self.max_batch,
                               max_prefill=int(self._eng.max_prefill),
-                              gqa_attention=self.gqa_attention)
+                              gqa_attention=self.gqa_attention,
+                              kv_dtype=self.kv_dtype)
         for li, (an, fn, mats) in enumerate(self._layers_cache):
             twin._eng.set_layer(li, an, fn, mats)
         twin._layers_cache = self._layers_cache  # enables further clones
@@ -404,8 +433,12 @@ class TorchSliceEngine:
 
     def __init__(self, hp: ggml.Hparams, weights: Dict[str, torch.Tensor],
                  n_layers: int, first_layer: int, n_ctx: int = 512,
-                 max_batch: int = 4, device: str = "cpu"):
+                 max_batch: int = 4, device: str = "cpu",
+                 kv_dtype: str = "f16"):
         self.hp = hp
+        # "q8": every K/V row is fake-quantised as it is stored
+        # (quantize_kv_rows), the CPU twin of the int8 KV cache
+        self.kv_dtype = _check_kv_dtype(kv_dtype)
         self.w = weights
         self.first_layer = first_layer
         self.n_layers = n_layers
@@ -422,12 +455,13 @@ class TorchSliceEngine:
 
     @classmethod
     def from_ggml(cls, f: ggml.GGMLFile, n_ctx: int = 512,
-                  max_batch: int = 4) -> "TorchSliceEngine":
+                  max_batch: int = 4,
+                  kv_dtype: str = "f16") -> "TorchSliceEngine":
         from ..models.llama import weights_from_ggml
         hp = f.hparams
         first = hp.first_layer if hp.first_layer is not None else 0
         return cls(hp, weights_from_ggml(f), hp.n_layer, first, n_ctx,
-                   max_batch)
+                   max_batch, kv_dtype=kv_dtype)
 
     def attach_extra(self, f: ggml.GGMLFile) -> None:
         from ..models.llama import weights_from_ggml
@@ -447,7 +481,10 @@ class TorchSliceEngine:
         kv_map = torch.arange(h) // (h // hkv)  # GQA head sharing
         pos_l = pos.tolist()
         seq_l = seq.tolist()
+        q8 = self.kv_dtype == "q8"
         if prefix is not None:
+            if q8:
+                raise ValueError("kv_dtype='q8' does not support prefix=")
             pslot, P, pfx = prefix
             pslot, P, pfx_l = int(pslot), int(P), pfx.tolist()
             if not 0 <= pslot < self.max_batch:
@@ -468,8 +505,9 @@ class TorchSliceEngine:
                 p, b = pos_l[t], seq_l[t]
                 qt = rope_interleaved(q[t:t + 1].view(1, h, d), p)[0]
                 kt = rope_interleaved(k[t:t + 1].view(1, hkv, d), p)[0]
-                self.k_cache[li, b, p] = kt
-                self.v_cache[li, b, p] = v[t].view(hkv, d)
+                vt = v[t].view(hkv, d)
+                self.k_cache[li, b, p] = quantize_kv_rows(kt) if q8 else kt
+                self.v_cache[li, b, p] = quantize_kv_rows(vt) if q8 else vt
                 keys = self.k_cache[li, b, :p + 1]
                 vals = self.v_cache[li, b, :p + 1]
                 if prefix is not None and pfx_l[t] > 0:
@@ -583,10 +621,12 @@ class TorchSliceEngine:
 
 
 def engine_for_slice(f: ggml.GGMLFile, n_ctx: int, max_batch: int,
-                     device: Optional[str] = None):
+                     device: Optional[str] = None, kv_dtype: str = "f16"):
     """Pick the engine for this machine: HIP when a GPU is present."""
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if device == "cuda":
-        return HIPSliceEngine.from_ggml(f, n_ctx=n_ctx, max_batch=max_batch)
-    return TorchSliceEngine.from_ggml(f, n_ctx=n_ctx, max_batch=max_batch)
+        return HIPSliceEngine.from_ggml(f, n_ctx=n_ctx, max_batch=max_batch,
+                                        kv_dtype=kv_dtype)
+    return TorchSliceEngine.from_ggml(f, n_ctx=n_ctx, max_batch=max_batch,
+                                      kv_dtype=kv_dtype)

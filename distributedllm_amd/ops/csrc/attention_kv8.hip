@@ -1,0 +1,509 @@
+// Int8 KV cache (kv_dtype = "q8", gfx950): the quantising append
+// `k_kv8_append` and the matrix-core attention kernel `k_attn_kv8` over the
+// byte caches, with their launchers (formats and semantics: kernels.h).
+//
+// A cache row of one KV head is D bytes u = q + 128, q in [-127, 127], and
+// one f16 scale s: x ~ s * q. 0x6400 | u is exactly the f16 value 1024 + u
+// (the byte-stream GEMMs' expansion, mfma_gemm.hip), so one v_perm_b32 and
+// one packed-f16 add of -1152 turn two bytes into two exact integer-valued
+// halves q: no convert instruction, and no value a byte could hold is
+// anything but a finite half.
+//
+// k_attn_kv8 has k_attn_gqa's work split (attention.hip): one block per
+// (token, KV head, up to 16 query heads of its group, KV chunk), the group's
+// query heads as the 16 MFMA columns, four waves that stream the chunk's
+// tiles with two tile buffers and merge once at the end; split partials go
+// to k_attn_gqa_merge unchanged. What differs is the data path:
+//   * a wave's tile is 32 rows, not 16: a 16-byte load brings 16 elements,
+//     so the same number of loads per lane as the f16 kernel (4 K + 4 V at
+//     D = 128) keeps the same bytes in flight and covers twice the rows;
+//   * scores: lane (row lq, lg) loads the 16 bytes d = c*64 + lg*16 .. + 15
+//     of its row for each 64-wide chunk c and feeds them to two
+//     mfma_f32_16x16x32_f16 as the k-span lg of each (the contraction index
+//     is permuted; the staged Q fragments follow the same permutation). The
+//     f32 score is then multiplied by s_k[row] / sqrt(D): the K scale is
+//     never applied per element;
+//   * PV: one mfma_f32_16x16x32_f16 per 16 d over all 32 rows. The B operand
+//     is P~ = p * s_v[row] / R packed to f16, in the score C layout of the
+//     tile's two 16-row halves (k-slot e of lane group lg is row
+//     (e / 4) * 16 + lg * 4 + e % 4); the A operand is the integer-valued
+//     V^T. R is the wave's running maximum of s_v over the attended rows it
+//     has seen, carried like the running score maximum: when it rises the
+//     accumulators are rescaled by R_old / R_new together with the softmax
+//     correction, and the wave's partial is multiplied by R once at the end.
+//     So P~ lies in [0, 1] whatever the magnitude of V, and its f16 rounding
+//     is that of the f16 p of the other matrix-core kernels (docs/kernels.md,
+//     "Int8 KV cache", has the bound);
+//   * V transpose for 1-byte elements: lane (quad g = lane / 8, span
+//     sp = lane % 8) loads rows g*4 .. g*4+3, bytes sp*16 .. +15, transposes
+//     the four 4x4 byte blocks in registers (8 v_perm_b32 each) into one
+//     u32 per d that holds the quad's four rows, and writes them as four
+//     16-byte LDS stores to vt[g][d]. The consumer lane (lq, lg) of d-chunk
+//     dc reads vt[lg][dc*16 + lq] and vt[4 + lg][dc*16 + lq]: its eight
+//     k-slots. KV8_VSTRIDE = 144 words puts the lane groups' 16-word reads
+//     on disjoint banks (144 mod 64 = 16);
+//   * the 32 K scales and 32 V scales of a tile arrive as one 2-byte load
+//     per lane and are redistributed through 128 bytes of wave-private LDS.
+// Every load is unconditional and every address valid, as in gqa_load_tile:
+// rows at or past the chunk end read row 0 and are masked, spans that start
+// at or past D read span 0 (K: multiplied by q = 0; V: columns that are
+// never stored), a span that straddles D reads into the next head or the
+// 16-byte pad. Head starts are multiples of 4 bytes (D % 4 == 0), which is
+// all a 16-byte global load needs.
+//
+// G = H / Hkv = 1 (MHA) runs the same kernel with one live MFMA column: the
+// kernel is bound by the byte stream and the expansion of the bytes, both of
+// which a VALU dot would pay as well, and one code path serves every G.
+
+#include <algorithm>
+
+#include "attn_common.h"
+#include "kernels.h"
+
+typedef __attribute__((ext_vector_type(2))) _Float16 kv8_f16x2;
+typedef __attribute__((ext_vector_type(4))) _Float16 kv8_f16x4;
+// 16 bytes at 4-byte alignment
+typedef uint32_t kv8_u32x4 __attribute__((ext_vector_type(4), aligned(4)));
+
+constexpr int KV8_MIN_CHUNK = 256;  // rows per split, lower bound (unmeasured)
+constexpr int KV8_MAX_SPLITS = 8;   // splits of a full context (unmeasured)
+constexpr int KV8_VSTRIDE = 144;    // u32 per row quad of a V tile
+
+int attn_kv8_chunk(int n_ctx) {
+    const int per = (n_ctx + KV8_MAX_SPLITS - 1) / KV8_MAX_SPLITS;
+    return std::max(KV8_MIN_CHUNK, (per + 63) & ~63);
+}
+
+int attn_kv8_splits(int n_ctx, int T) {
+    if (T > 64) return 1;  // wide launches fill the chip by themselves
+    const int chunk = attn_kv8_chunk(n_ctx);
+    return (n_ctx + chunk - 1) / chunk;
+}
+
+// ------------------------------------------------------------------ append
+// Wave = (token, KV head); lanes 0..31 quantise the K row of the head, lanes
+// 32..63 the V row, four elements each (D <= 128). amax is reduced inside
+// the half wave, the bytes leave as one 4-byte store per lane.
+GQA_FN __global__ __launch_bounds__(BLOCK) void k_kv8_append(
+    const __half* __restrict__ k_stage, const __half* __restrict__ v_stage,
+    uint8_t* __restrict__ k8, uint8_t* __restrict__ v8,
+    __half* __restrict__ k_scale, __half* __restrict__ v_scale,
+    const int* __restrict__ pos, const int* __restrict__ seq, int T, int Hkv,
+    int D, int n_ctx) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int unit = (int)blockIdx.x * NWAVES + (int)threadIdx.x / WAVE;
+    if (unit >= T * Hkv) return;        // wave-uniform
+    const int t = unit / Hkv;
+    const int hk = unit % Hkv;
+    const bool isv = lane >= 32;
+    const int d0 = (lane & 31) * 4;
+    const bool dok = d0 < D;
+    const size_t row = (size_t)seq[t] * n_ctx + pos[t];
+    const size_t off = row * ((size_t)Hkv * D) + (size_t)hk * D +
+                       (dok ? d0 : 0);  // lanes past D reread the head start
+    const uint2 raw =
+        *reinterpret_cast<const uint2*>((isv ? v_stage : k_stage) + off);
+    const kv8_f16x4 h = __builtin_bit_cast(kv8_f16x4, raw);
+    float x[4], amax = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        x[i] = dok ? (float)h[i] : 0.0f;
+        amax = fmaxf(amax, fabsf(x[i]));
+    }
+#pragma unroll
+    for (int sh = 1; sh <= 16; sh <<= 1)
+        amax = fmaxf(amax, gqa_shfl_xor(amax, lane, sh));
+    const _Float16 s16 = (_Float16)(amax / 127.0f);
+    const float s = (float)s16;
+    uint32_t packed = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float q = (s > 0.0f) ? __builtin_rintf(x[i] / s) : 0.0f;
+        q = fminf(fmaxf(q, -127.0f), 127.0f);
+        packed |= (uint32_t)((int)q + 128) << (8 * i);
+    }
+    if (dok)
+        *reinterpret_cast<uint32_t*>((isv ? v8 : k8) + off) = packed;
+    if ((lane & 31) == 0)
+        reinterpret_cast<unsigned short*>(isv ? v_scale : k_scale)
+            [row * Hkv + hk] = __builtin_bit_cast(unsigned short, s16);
+}
+
+// --------------------------------------------------------------- attention
+
+// Four bytes of w -> exact integer-valued halves (b0 - 128, b1 - 128) and
+// (b2 - 128, b3 - 128): 0x64bb is f16(1024 + b)
+GQA_FN __device__ __forceinline__ void kv8_expand4(uint32_t w, uint32_t& lo,
+                                                   uint32_t& hi) {
+    const kv8_f16x2 c = {(_Float16)-1152.0f, (_Float16)-1152.0f};
+    const uint32_t a = __builtin_amdgcn_perm(0x64646464u, w, 0x04010400u);
+    const uint32_t b = __builtin_amdgcn_perm(0x64646464u, w, 0x04030402u);
+    lo = __builtin_bit_cast(uint32_t, __builtin_bit_cast(kv8_f16x2, a) + c);
+    hi = __builtin_bit_cast(uint32_t, __builtin_bit_cast(kv8_f16x2, b) + c);
+}
+
+// One 32-row tile of one wave as loaded: K in score-A order (lane: rows lq
+// and 16 + lq, 16 bytes of each 64-d chunk), V row-major (lane: rows
+// (lane/8)*4 + e, bytes (lane%8)*16 .. +15), and one scale (lanes 0..31 the
+// K scale of row lane, lanes 32..63 the V scale of row lane - 32).
+template <int NSC>
+struct Kv8Tile {
+    kv8_u32x4 k[2][NSC];
+    kv8_u32x4 v[4];
+    unsigned short sc;
+};
+
+// gqa_load_tile's rules: straight-line loads with no branch around them,
+// every address valid, pinned above the caller's next step.
+template <int NSC>
+GQA_FN __device__ __forceinline__ void kv8_load_tile(
+    Kv8Tile<NSC>& t, const uint8_t* __restrict__ kb,
+    const uint8_t* __restrict__ vb, const unsigned short* __restrict__ ksb,
+    const unsigned short* __restrict__ vsb, int tj, int jend, int Ekv,
+    int Hkv, int D, int lane) {
+    const int lq = lane & 15;
+    const int lg = lane >> 4;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int jk = tj + r * 16 + lq;
+        const uint8_t* krow = kb + (size_t)(jk < jend ? jk : 0) * Ekv;
+#pragma unroll
+        for (int c = 0; c < NSC; ++c) {
+            const int d0 = c * 64 + lg * 16;
+            t.k[r][c] = *reinterpret_cast<const kv8_u32x4*>(
+                krow + (d0 < D ? d0 : 0));
+        }
+    }
+    const int dv = ((lane & 7) * 16 < D) ? (lane & 7) * 16 : 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int jv = tj + (lane >> 3) * 4 + e;
+        const uint8_t* vrow = vb + (size_t)(jv < jend ? jv : 0) * Ekv;
+        t.v[e] = *reinterpret_cast<const kv8_u32x4*>(vrow + dv);
+    }
+    const int js = tj + (lane & 31);
+    t.sc = (lane < 32 ? ksb : vsb)[(size_t)(js < jend ? js : 0) * Hkv];
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// V transpose (file header). The lane holds V[g*4 + e][sp*16 + i], e = 0..3,
+// i = 0..15; word w of its four rows is a 4x4 byte block that two rounds of
+// v_perm_b32 turn into four words {V[g*4 + 0..3][d]}, d = sp*16 + 4w + 0..3.
+GQA_FN __device__ __forceinline__ void kv8_stage_v(
+    uint32_t* __restrict__ vt, const kv8_u32x4 v[4], int lane) {
+    uint4* dst = reinterpret_cast<uint4*>(
+        vt + (lane >> 3) * KV8_VSTRIDE + (lane & 7) * 16);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint32_t t01l = __builtin_amdgcn_perm(v[1][w], v[0][w],
+                                                    0x05010400u);
+        const uint32_t t01h = __builtin_amdgcn_perm(v[1][w], v[0][w],
+                                                    0x07030602u);
+        const uint32_t t23l = __builtin_amdgcn_perm(v[3][w], v[2][w],
+                                                    0x05010400u);
+        const uint32_t t23h = __builtin_amdgcn_perm(v[3][w], v[2][w],
+                                                    0x07030602u);
+        uint4 o;
+        o.x = __builtin_amdgcn_perm(t23l, t01l, 0x05040100u);   // d = 4w
+        o.y = __builtin_amdgcn_perm(t23l, t01l, 0x07060302u);
+        o.z = __builtin_amdgcn_perm(t23h, t01h, 0x05040100u);
+        o.w = __builtin_amdgcn_perm(t23h, t01h, 0x07060302u);
+        dst[w] = o;
+    }
+}
+
+// One 32-row tile of one wave: scores, online softmax on the score C layout
+// of the two 16-row halves, V transpose, PV. (m, l) are the running max and
+// sum of column lq, R the running maximum of the V scales (wave-uniform).
+template <int DC, int NSC>
+GQA_FN __device__ __forceinline__ void kv8_tile_step(
+    const Kv8Tile<NSC>& tile, const ABFrag (&qf)[2 * NSC], uint32_t* vt,
+    _Float16* st, int tj, int ce, int lane, float qk_scale, float& m,
+    float& l, float& R, f32x4 (&oacc)[DC]) {
+    const int lq = lane & 15;
+    const int lg = lane >> 4;
+    f32x4 sc[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        sc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < NSC; ++c) {
+            ABFrag ka, kb;
+            kv8_expand4(tile.k[r][c][0], ka.u[0], ka.u[1]);
+            kv8_expand4(tile.k[r][c][1], ka.u[2], ka.u[3]);
+            kv8_expand4(tile.k[r][c][2], kb.u[0], kb.u[1]);
+            kv8_expand4(tile.k[r][c][3], kb.u[2], kb.u[3]);
+            sc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                ka.v, qf[2 * c].v, sc[r], 0, 0, 0);
+            sc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                kb.v, qf[2 * c + 1].v, sc[r], 0, 0, 0);
+        }
+    }
+    reinterpret_cast<unsigned short*>(st)[lane] = tile.sc;
+    kv8_stage_v(vt, tile.v, lane);
+    gqa_wave_sync();                        // scales, V tile written -> read
+
+    // lane holds s[j = tj + r*16 + lg*4 + jj][column lq] as slot r*4 + jj
+    float s[8], sv[8], tm = -INFINITY, svm = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const kv8_f16x4 ks =
+            *reinterpret_cast<const kv8_f16x4*>(st + r * 16 + lg * 4);
+        const kv8_f16x4 vs =
+            *reinterpret_cast<const kv8_f16x4*>(st + 32 + r * 16 + lg * 4);
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const bool ok = tj + r * 16 + lg * 4 + jj < ce;
+            s[r * 4 + jj] = ok ? sc[r][jj] * ((float)ks[jj] * qk_scale)
+                               : -INFINITY;
+            sv[r * 4 + jj] = ok ? (float)vs[jj] : 0.0f;
+            tm = fmaxf(tm, s[r * 4 + jj]);
+            svm = fmaxf(svm, sv[r * 4 + jj]);
+        }
+    }
+    tm = fmaxf(tm, gqa_shfl_xor(tm, lane, 16));
+    tm = fmaxf(tm, gqa_shfl_xor(tm, lane, 32));
+    svm = fmaxf(svm, gqa_shfl_xor(svm, lane, 16));
+    svm = fmaxf(svm, gqa_shfl_xor(svm, lane, 32));
+    // finite: the wave's first tile has an attended row. A tile wholly past
+    // the chunk (tm = -inf, svm = 0) leaves m, l, R and oacc as they are.
+    const float m_new = fmaxf(m, tm);
+    const float R_new = fmaxf(R, svm);
+    const float inv_r = (R_new > 0.0f) ? __builtin_amdgcn_rcpf(R_new) : 0.0f;
+    const float alpha = __expf(m - m_new);  // 0 on the first tile
+    // accumulators are in units of R: exactly 1 while R stands
+    const float alpha_o = alpha * ((R_new == R) ? 1.0f : R * inv_r);
+    float ts = 0.0f, pt[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float p = __expf(s[e] - m_new);   // 0 for masked rows
+        ts += p;
+        pt[e] = p * (sv[e] * inv_r);            // P~ in [0, 1]
+    }
+    ABFrag p;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        p.u[i] = gqa_pack_f16(pt[2 * i], pt[2 * i + 1]);
+    ts += gqa_shfl_xor(ts, lane, 16);
+    ts += gqa_shfl_xor(ts, lane, 32);
+    l = l * alpha + ts;
+    m = m_new;
+    R = R_new;
+
+    // the accumulators leave the MFMA register file only when some column's
+    // factor is not 1 (wave-uniform branch; x * 1 is x)
+    if (__builtin_amdgcn_ballot_w64(alpha_o != 1.0f) != 0) {
+#pragma unroll
+        for (int dc = 0; dc < DC; ++dc) {
+            oacc[dc][0] *= alpha_o; oacc[dc][1] *= alpha_o;
+            oacc[dc][2] *= alpha_o; oacc[dc][3] *= alpha_o;
+        }
+    }
+#pragma unroll
+    for (int dc = 0; dc < DC; ++dc) {
+        ABFrag vf;
+        kv8_expand4(vt[lg * KV8_VSTRIDE + dc * 16 + lq], vf.u[0], vf.u[1]);
+        kv8_expand4(vt[(4 + lg) * KV8_VSTRIDE + dc * 16 + lq], vf.u[2],
+                    vf.u[3]);
+        oacc[dc] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf.v, p.v,
+                                                          oacc[dc], 0, 0, 0);
+    }
+    gqa_wave_sync();                        // read -> next tile's write
+}
+
+// DC = 16-wide d chunks of the PV product, a power of two >= D/16; the score
+// product runs NSC = max(1, DC/4) 64-wide chunks of two MFMAs each. Chunks
+// past D work on zero q (scores) or produce columns that are never stored.
+template <int DC>
+GQA_FN __global__ __launch_bounds__(BLOCK) void k_attn_kv8(
+    const float* __restrict__ q_buf, const uint8_t* __restrict__ k8,
+    const uint8_t* __restrict__ v8, const __half* __restrict__ k_scale,
+    const __half* __restrict__ v_scale, float* __restrict__ out,
+    unsigned short* __restrict__ out_prep, const int* __restrict__ pos,
+    const int* __restrict__ seq, float* __restrict__ ws, int H, int grp,
+    int E, int Ekv, int D, int n_ctx, int jtw, int chunk) {
+    constexpr int NSC = DC > 4 ? DC / 4 : 1;
+    constexpr int QW = NSC * 64;        // staged q row, halves
+    const int t = blockIdx.x;
+    const int J = pos[t] + 1;
+    const int cs = (int)blockIdx.z * chunk;
+    if (cs >= J) return;                // block-uniform
+    const int ce = min(J, cs + chunk);
+    const int ntile = (grp + 15) >> 4;  // column tiles per KV head
+    const int hk = (int)blockIdx.y / ntile;
+    const int c0 = ((int)blockIdx.y % ntile) * 16;  // first column's head
+    const int ncol = min(16, grp - c0);
+    const int Hkv = Ekv / D;
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = __builtin_amdgcn_readfirstlane(tid / WAVE);  // scalar
+    const int lq = lane & 15;
+    const int lg = lane >> 4;
+    const size_t row0 = (size_t)seq[t] * n_ctx;
+    const uint8_t* kb = k8 + row0 * Ekv + hk * D;
+    const uint8_t* vb = v8 + row0 * Ekv + hk * D;
+    const unsigned short* ksb =
+        reinterpret_cast<const unsigned short*>(k_scale) + row0 * Hkv + hk;
+    const unsigned short* vsb =
+        reinterpret_cast<const unsigned short*>(v_scale) + row0 * Hkv + hk;
+
+    // One LDS region, used twice: the waves' V tiles and scales and the
+    // staged Q while streaming, the waves' O partials [w][col][OSTR] after
+    // it (OSTR skews the 16 columns by 4 banks each).
+    constexpr int OSTR = DC * 16 + 4;
+    constexpr int VT_BYTES = NWAVES * 8 * KV8_VSTRIDE * (int)sizeof(uint32_t);
+    constexpr int SC_BYTES = NWAVES * 64 * (int)sizeof(_Float16);
+    constexpr int Q_BYTES = 16 * (QW + 8) * (int)sizeof(_Float16);
+    constexpr int O_BYTES = NWAVES * 16 * OSTR * (int)sizeof(float);
+    constexpr int S_BYTES = VT_BYTES + SC_BYTES + Q_BYTES;
+    constexpr int LDS_BYTES = S_BYTES > O_BYTES ? S_BYTES : O_BYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
+    __shared__ float lds_m[NWAVES][16];
+    __shared__ float lds_l[NWAVES][16];
+    uint32_t* vt = reinterpret_cast<uint32_t*>(lds_raw) +
+                   wid * 8 * KV8_VSTRIDE;
+    _Float16* st = reinterpret_cast<_Float16*>(lds_raw + VT_BYTES) + wid * 64;
+    _Float16 (*lds_q)[QW + 8] = reinterpret_cast<_Float16 (*)[QW + 8]>(
+        lds_raw + VT_BYTES + SC_BYTES);
+    float* lds_o = reinterpret_cast<float*>(lds_raw);
+
+    // Q tile -> LDS as f16, zero past D and past the group's last head (the
+    // factor, not a branch, does the masking: the loads stay independent).
+    // The ncol heads are contiguous in q_buf. 1/sqrt(D) joins the K scale.
+    {
+        const float* qt = q_buf + (size_t)t * E + (size_t)(hk * grp + c0) * D;
+#pragma unroll
+        for (int i = 0; i < 16 * QW / BLOCK; ++i) {
+            const int idx = tid + i * BLOCK;
+            const int col = idx / QW;
+            const int d = idx % QW;
+            const bool ok = col < ncol && d < D;
+            const float v = qt[ok ? col * D + d : 0] * (ok ? 1.0f : 0.0f);
+            lds_q[col][d] = (_Float16)v;
+        }
+    }
+    gqa_block_sync();
+    // score-MFMA B fragments: lane (column lq, lg) holds d = c*64 + lg*16 +
+    // 0..7 for the first MFMA of chunk c and + 8..15 for the second
+    ABFrag qf[2 * NSC];
+#pragma unroll
+    for (int c = 0; c < 2 * NSC; ++c) {
+        const uint4 u = *reinterpret_cast<const uint4*>(
+            &lds_q[lq][(c >> 1) * 64 + lg * 16 + (c & 1) * 8]);
+        qf[c].u[0] = u.x; qf[c].u[1] = u.y;
+        qf[c].u[2] = u.z; qf[c].u[3] = u.w;
+    }
+    const float qk_scale = rsqrtf((float)D);
+
+    float m = -INFINITY, l = 0.0f;      // running state of column lq
+    float R = 0.0f;                     // running max of the V scales
+    f32x4 oacc[DC];
+#pragma unroll
+    for (int dc = 0; dc < DC; ++dc) oacc[dc] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // Wave w streams tiles w, w+4, ... of the chunk, two per iteration in
+    // two buffers that swap roles; every tile's loads are issued one tile
+    // ahead (k_attn_gqa's loop). An odd tile count ends with one tile wholly
+    // past the chunk, which reads row 0, is masked and changes nothing.
+    constexpr int STEP = NWAVES * 32;
+    int tj = cs + wid * 32;
+    if (tj < ce) {                      // wave-uniform, scalar
+        Kv8Tile<NSC> cur, alt;
+        kv8_load_tile(cur, kb, vb, ksb, vsb, tj, ce, Ekv, Hkv, D, lane);
+        do {
+            kv8_load_tile(alt, kb, vb, ksb, vsb, tj + STEP, ce, Ekv, Hkv, D,
+                          lane);
+            kv8_tile_step<DC, NSC>(cur, qf, vt, st, tj, ce, lane, qk_scale,
+                                   m, l, R, oacc);
+            kv8_load_tile(cur, kb, vb, ksb, vsb, tj + 2 * STEP, ce, Ekv, Hkv,
+                          D, lane);
+            kv8_tile_step<DC, NSC>(alt, qf, vt, st, tj + STEP, ce, lane,
+                                   qk_scale, m, l, R, oacc);
+            tj += 2 * STEP;
+        } while (tj < ce);
+    }
+    gqa_block_sync();                   // tiles and Q are dead: reuse LDS
+
+    // merge the 4 waves' partials in wave order (lane group 0 holds the
+    // column's (m, l); oacc[dc][jj] * R is O[d = dc*16 + lg*4 + jj][col lq])
+    if (lg == 0) {
+        lds_m[wid][lq] = m;
+        lds_l[wid][lq] = l;
+    }
+#pragma unroll
+    for (int dc = 0; dc < DC; ++dc) {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+            lds_o[(wid * 16 + lq) * OSTR + dc * 16 + lg * 4 + jj] =
+                oacc[dc][jj] * R;
+    }
+    gqa_block_sync();
+    const int col = tid >> 4;
+    if (col >= ncol) return;
+    const int h = hk * grp + c0 + col;
+    float mstar = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) mstar = fmaxf(mstar, lds_m[w][col]);
+    float wsc[NWAVES], lstar = 0.0f;
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) {
+        const float mw = lds_m[w][col];         // -inf: wave had no tile
+        wsc[w] = (mw == -INFINITY) ? 0.0f : __expf(mw - mstar);
+        lstar += lds_l[w][col] * wsc[w];
+    }
+    const bool whole = J <= chunk;      // the token's only chunk: final
+    float* part = ws + (((size_t)t * H + h) * gridDim.z + blockIdx.z) *
+                           (size_t)(D + 2);
+    if (!whole && (tid & 15) == 0) {
+        part[0] = mstar;
+        part[1] = lstar;
+    }
+    for (int d = tid & 15; d < D; d += 16) {
+        float ostar = 0.0f;
+#pragma unroll
+        for (int w = 0; w < NWAVES; ++w)
+            ostar += lds_o[(w * 16 + col) * OSTR + d] * wsc[w];
+        if (!whole) {
+            part[2 + d] = ostar;
+            continue;
+        }
+        gqa_store_out(ostar / lstar, h * D + d, t, E, jtw, out, out_prep);
+    }
+}
+
+// ============================================================== launchers
+
+void launch_kv8_append(hipStream_t s, const __half* k_stage,
+                       const __half* v_stage, uint8_t* k8_layer,
+                       uint8_t* v8_layer, __half* k_scale_layer,
+                       __half* v_scale_layer, const int* pos, const int* seq,
+                       int T, int Hkv, int D, int n_ctx) {
+    hipLaunchKernelGGL(k_kv8_append, dim3((T * Hkv + NWAVES - 1) / NWAVES),
+                       dim3(BLOCK), 0, s, k_stage, v_stage, k8_layer,
+                       v8_layer, k_scale_layer, v_scale_layer, pos, seq, T,
+                       Hkv, D, n_ctx);
+}
+
+void launch_attn_kv8(hipStream_t s, const float* q_buf,
+                     const uint8_t* k8_layer, const uint8_t* v8_layer,
+                     const __half* k_scale_layer,
+                     const __half* v_scale_layer, float* out,
+                     unsigned short* out_prep, const int* pos,
+                     const int* seq, int T, int H, int Hkv, int E, int Ekv,
+                     int D, int n_ctx, float* ws) {
+    const int grp = H / Hkv;
+    const int S = attn_kv8_splits(n_ctx, T);
+    // one split covers the whole context, whatever its length
+    const int chunk = (S == 1) ? std::max(n_ctx, KV8_MIN_CHUNK)
+                               : attn_kv8_chunk(n_ctx);
+    const int jtw = jt_width(T);
+    const dim3 grid(T, Hkv * ((grp + 15) / 16), S);
+    auto kern = D <= 16 ? k_attn_kv8<1> : D <= 32 ? k_attn_kv8<2>
+              : D <= 64 ? k_attn_kv8<4> : k_attn_kv8<8>;
+    hipLaunchKernelGGL(kern, grid, dim3(BLOCK), 0, s, q_buf, k8_layer,
+                       v8_layer, k_scale_layer, v_scale_layer, out, out_prep,
+                       pos, seq, ws, H, grp, E, Ekv, D, n_ctx, jtw, chunk);
+    if (S > 1)
+        launch_attn_gqa_merge(s, ws, out, out_prep, pos, T, H, E, D, jtw,
+                              chunk, S);
+}

@@ -64,6 +64,11 @@ int64_t prefix_ws_numel(int64_t H, int64_t D, int64_t n_ctx, int64_t max_t) {
                max_t) * H * (D + 2);
 }
 
+// split-KV partials of launch_attn_kv8: the same layout at its own splits
+int64_t kv8_ws_numel(int64_t H, int64_t D, int64_t n_ctx) {
+    return (int64_t)kMaxTokens * H * attn_kv8_splits((int)n_ctx, 1) * (D + 2);
+}
+
 int64_t slab_numel(int64_t tiles, int64_t ks = kMaxSplit) {
     return tiles * ks * kMaxTokens * 16;
 }
@@ -186,7 +191,8 @@ class SliceEngine {
     SliceEngine(int64_t n_embd, int64_t n_head, int64_t n_layers,
                 int64_t n_ff, int64_t n_ctx, int64_t max_batch, double eps,
                 double rope_base, int64_t max_prefill = 1024,
-                int64_t n_head_kv = 0, bool gqa_attention = true)
+                int64_t n_head_kv = 0, bool gqa_attention = true,
+                int64_t kv_dtype = 0)
         : E_((int)n_embd),
           H_((int)n_head),
           D_((int)(n_embd / n_head)),
@@ -195,7 +201,10 @@ class SliceEngine {
           ctx_((int)n_ctx),
           B_((int)max_batch),
           eps_((float)eps),
-          gqa_attention_(gqa_attention) {
+          gqa_attention_(gqa_attention),
+          kv8_(kv_dtype == 1) {
+        TORCH_CHECK(kv_dtype == 0 || kv_dtype == 1,
+                    "kv_dtype must be 0 (f16) or 1 (q8)");
         TORCH_CHECK(E_ % H_ == 0, "n_embd not divisible by n_head");
         TORCH_CHECK(D_ % 2 == 0, "head_dim must be even for RoPE pairs");
         TORCH_CHECK(D_ <= 128, "head_dim > 128 unsupported (the "
@@ -206,6 +215,10 @@ class SliceEngine {
         TORCH_CHECK(H_ % HK_ == 0, "n_head not divisible by n_head_kv");
         EK_ = HK_ * D_;
         TORCH_CHECK(EK_ % 16 == 0, "kv width must be 16-aligned");
+        TORCH_CHECK(!kv8_ || D_ % 4 == 0,
+                    "kv_dtype q8 needs head_dim % 4 == 0");
+        TORCH_CHECK(!kv8_ || H_ / HK_ <= 64,
+                    "kv_dtype q8 serves n_head / n_head_kv <= 64");
         // prefill token cap per forward call: side channels and q/attn
         // buffers scale with it (a few hundred MB at 2048 on 65B shapes)
         maxP_ = std::max((int)max_prefill, kMaxTokens);
@@ -221,9 +234,26 @@ class SliceEngine {
         // Ekv = Hkv*D < E under GQA. 16 halves of tail pad let the
         // attention kernels read whole 16 B octets unconditionally at
         // the last row (no divergent tail-load branches).
+        // kv_dtype q8 (attention_kv8.hip): the same shape in re-biased
+        // bytes (128 = 0) with 16 bytes of pad, f16 scale planes
+        // [L, B, ctx, Hkv], one single-layer f16 stage per K and V that the
+        // qkv kernels write and k_kv8_append quantises, and the split-KV
+        // workspace of k_attn_kv8.
         const int64_t kv_elems = (int64_t)L_ * B_ * ctx_ * EK_;
-        kv_store_k_ = torch::zeros({kv_elems + 16}, f16);
-        kv_store_v_ = torch::zeros({kv_elems + 16}, f16);
+        if (kv8_) {
+            auto u8 = dev.dtype(torch::kUInt8);
+            kv_store_k_ = torch::full({kv_elems + 16}, 128, u8);
+            kv_store_v_ = torch::full({kv_elems + 16}, 128, u8);
+            k_scale_ = torch::zeros({L_, B_, ctx_, HK_}, f16);
+            v_scale_ = torch::zeros({L_, B_, ctx_, HK_}, f16);
+            const int64_t stage = (int64_t)B_ * ctx_ * EK_ + 16;
+            k_stage_ = torch::zeros({stage}, f16);
+            v_stage_ = torch::zeros({stage}, f16);
+            kv8_ws_ = torch::zeros({kv8_ws_numel(H_, D_, ctx_)}, f32);
+        } else {
+            kv_store_k_ = torch::zeros({kv_elems + 16}, f16);
+            kv_store_v_ = torch::zeros({kv_elems + 16}, f16);
+        }
         k_cache_ = kv_store_k_.narrow(0, 0, kv_elems)
                        .view({L_, B_, ctx_, EK_});
         v_cache_ = kv_store_v_.narrow(0, 0, kv_elems)
@@ -274,6 +304,8 @@ class SliceEngine {
         l.mfma = (wt0 != W_F32);
         TORCH_CHECK(l.mfma || EK_ == E_,
                     "the legacy f32 path does not support GQA");
+        TORCH_CHECK(l.mfma || !kv8_,
+                    "the legacy f32 path does not support kv_dtype q8");
         DevMat* slots[7] = {&l.wq, &l.wk, &l.wv, &l.wo, &l.w1, &l.w2, &l.w3};
         DevMat2* slots2[7] = {&l.mq, &l.mk, &l.mv, &l.mo, &l.m1, &l.m2,
                               &l.m3};
@@ -363,9 +395,16 @@ class SliceEngine {
         float* xp = x.data_ptr<float>();
         const int* pp = pos.data_ptr<int>();
         const int* sp = seq.data_ptr<int>();
+        TORCH_CHECK(!kv8_ || prefix.is_none(),
+                    "kv_dtype q8 does not support prefix (shared-prefix "
+                    "attention reads an f16 cache)");
         const size_t layer_stride = (size_t)B_ * ctx_ * EK_;
-        __half* kbase = reinterpret_cast<__half*>(k_cache_.data_ptr());
-        __half* vbase = reinterpret_cast<__half*>(v_cache_.data_ptr());
+        // q8: byte caches, addressed through k8/v8 below; the f16 kernels
+        // see the single-layer stages
+        __half* kbase = kv8_ ? nullptr
+                             : reinterpret_cast<__half*>(k_cache_.data_ptr());
+        __half* vbase = kv8_ ? nullptr
+                             : reinterpret_cast<__half*>(v_cache_.data_ptr());
         const float* ifr = inv_freq_.data_ptr<float>();
         float* qb = qb_.data_ptr<float>();
         float* ab = ab_.data_ptr<float>();
@@ -438,20 +477,42 @@ class SliceEngine {
                                      gqa_attention_ ? 1 : 0);
         for (int li = 0; li < L_; ++li) {
             Layer& l = layers_[li];
-            __half* kc = kbase + (size_t)li * layer_stride;
-            __half* vc = vbase + (size_t)li * layer_stride;
-            // the GQA kernel has no fused prologue: k_qkv_finish runs
+            __half* kc = kv8_ ? reinterpret_cast<__half*>(k_stage_.data_ptr())
+                              : kbase + (size_t)li * layer_stride;
+            __half* vc = kv8_ ? reinterpret_cast<__half*>(v_stage_.data_ptr())
+                              : vbase + (size_t)li * layer_stride;
+            // the GQA and q8 kernels have no fused prologue: k_qkv_finish
+            // runs
             const int slab_used = launch_qkv16(
                 s, l.mq.w, l.mk.w, l.mv.w, xprep, u16p(l.attn_normprep),
                 ssa + li * ssw_, eps_, qb, kc, vc, pp, sp, ifr, E_, EK_,
                 D_, ctx_, T, slab,
-                /*skip_finish=*/(decode && route != 2 && !shared) ? 1 : 0);
+                /*skip_finish=*/
+                (decode && route != 2 && !shared && !kv8_) ? 1 : 0);
             ck("qkv", li);
             // 16-query tiles are spans for prefill; the distinct-sequence
             // decode shape streams per token at any T, fused with the
             // un-combined qkv slabs when the slab route ran; GQA models
             // run every such call on the (token, KV head) MFMA kernel
-            if (shared) {
+            if (kv8_) {
+                // every T: quantise the rows just staged, then attend over
+                // the layer's byte cache
+                uint8_t* k8 = k_cache_.data_ptr<uint8_t>() +
+                              (size_t)li * layer_stride;
+                uint8_t* v8 = v_cache_.data_ptr<uint8_t>() +
+                              (size_t)li * layer_stride;
+                const size_t sc_stride = (size_t)B_ * ctx_ * HK_;
+                __half* ksc = reinterpret_cast<__half*>(k_scale_.data_ptr()) +
+                              (size_t)li * sc_stride;
+                __half* vsc = reinterpret_cast<__half*>(v_scale_.data_ptr()) +
+                              (size_t)li * sc_stride;
+                launch_kv8_append(s, kc, vc, k8, v8, ksc, vsc, pp, sp, T,
+                                  HK_, D_, ctx_);
+                ck("kv8 append", li);
+                launch_attn_kv8(s, qb, k8, v8, ksc, vsc, ab, aprep, pp, sp,
+                                T, H_, HK_, E_, EK_, D_, ctx_,
+                                kv8_ws_.data_ptr<float>());
+            } else if (shared) {
                 launch_attn_prefix(s, qb, kc, vc, ab, aprep, pp, sp, fp,
                                    pslot, plen, T, H_, HK_, E_, EK_, D_,
                                    ctx_, prefix_ws_.data_ptr<float>());
@@ -677,9 +738,12 @@ class SliceEngine {
     int64_t max_prefill() const { return maxP_; }
     int64_t n_ctx() const { return ctx_; }
     int64_t max_batch() const { return B_; }
-    // the per-layer KV tensors ([L, B, ctx, E] f16)
+    // the per-layer KV tensors ([L, B, ctx, Ekv] f16; under q8 re-biased
+    // bytes, with the f16 scales [L, B, ctx, Hkv] beside them)
     torch::Tensor k_cache() const { return k_cache_; }
     torch::Tensor v_cache() const { return v_cache_; }
+    torch::Tensor k_scale() const { return k_scale_; }
+    torch::Tensor v_scale() const { return v_scale_; }
 
  private:
     void forward_legacy(hipStream_t s, float* xp, const int* pp,
@@ -714,6 +778,7 @@ class SliceEngine {
     int V_ = 0;
     float eps_;
     bool gqa_attention_;     // GQA models: route attention to k_attn_gqa
+    bool kv8_;               // kv_dtype q8: byte caches, k_attn_kv8
     std::vector<Layer> layers_;
     std::vector<bool> loaded_;
     torch::Tensor kv_store_k_, kv_store_v_;
@@ -722,6 +787,8 @@ class SliceEngine {
     torch::Tensor xprep_, aprep_, gprep_, ss_attn_, ss_ffn_, ss_tmp_;
     torch::Tensor argmax_keys_, slab_, gqa_ws_;
     torch::Tensor prefix_ws_;  // allocated by the first forward with prefix
+    // kv_dtype q8 only: scale planes, single-layer f16 stages, split-KV ws
+    torch::Tensor k_scale_, v_scale_, k_stage_, v_stage_, kv8_ws_;
     // prompt scoring, allocated by the first score() call
     torch::Tensor ss_score_, score_key_, score_sum_, score_tgt_;
     bool has_extra_ = false;
@@ -754,10 +821,9 @@ torch::Tensor check_f16_store(const torch::Tensor& t, const AttnDims& d,
     return t;
 }
 
-AttnDims check_attn_args(int64_t T, int64_t n_head, int64_t n_head_kv,
+// everything but the stores
+AttnDims check_attn_dims(int64_t T, int64_t n_head, int64_t n_head_kv,
                          int64_t head_dim, int64_t n_ctx, int64_t n_slots,
-                         const torch::Tensor& k_store,
-                         const torch::Tensor& v_store,
                          const torch::Tensor& pos,
                          const torch::Tensor& seq) {
     TORCH_CHECK(T >= 1 && T <= 4096, "token count out of range");
@@ -780,8 +846,6 @@ AttnDims check_attn_args(int64_t T, int64_t n_head, int64_t n_head_kv,
     d.slots = (int)n_slots;
     TORCH_CHECK(d.E % 16 == 0 && d.Ekv % 16 == 0,
                 "E and Ekv must be multiples of 16");
-    check_f16_store(k_store, d, "k_store");
-    check_f16_store(v_store, d, "v_store");
     check_i32(pos, "pos");
     check_i32(seq, "seq");
     TORCH_CHECK(pos.dim() == 1 && seq.dim() == 1 && pos.numel() == T &&
@@ -794,6 +858,19 @@ AttnDims check_attn_args(int64_t T, int64_t n_head, int64_t n_head_kv,
     TORCH_CHECK(seq.min().item<int64_t>() >= 0 &&
                     seq.max().item<int64_t>() < n_slots,
                 "seq out of [0, n_slots)");
+    return d;
+}
+
+AttnDims check_attn_args(int64_t T, int64_t n_head, int64_t n_head_kv,
+                         int64_t head_dim, int64_t n_ctx, int64_t n_slots,
+                         const torch::Tensor& k_store,
+                         const torch::Tensor& v_store,
+                         const torch::Tensor& pos,
+                         const torch::Tensor& seq) {
+    const AttnDims d = check_attn_dims(T, n_head, n_head_kv, head_dim, n_ctx,
+                                       n_slots, pos, seq);
+    check_f16_store(k_store, d, "k_store");
+    check_f16_store(v_store, d, "v_store");
     return d;
 }
 
@@ -863,6 +940,78 @@ AttnResult attention_decode_gqa(torch::Tensor q, torch::Tensor k_store,
         torch::TensorOptions().device(torch::kCUDA).dtype(torch::kFloat32));
     hipStream_t s = c10::hip::getCurrentHIPStream().stream();
     launch_attn_gqa(s, q.data_ptr<float>(), h16c(k_store), h16c(v_store),
+                    std::get<0>(r).data_ptr<float>(), u16p(std::get<1>(r)),
+                    pos.data_ptr<int>(), seq.data_ptr<int>(), d.T, d.H,
+                    d.Hkv, d.E, d.Ekv, d.D, d.ctx, ws.data_ptr<float>());
+    return r;
+}
+
+// q8 stores of the int8-KV hooks: bytes u8 [n_slots*n_ctx*Ekv + 16] (the
+// pad is mandatory: the kernel reads whole 16-byte spans past the last
+// head) and scales f16 [n_slots*n_ctx*Hkv]
+void check_kv8_stores(const AttnDims& d, const torch::Tensor& k8,
+                      const torch::Tensor& v8, const torch::Tensor& ksc,
+                      const torch::Tensor& vsc) {
+    TORCH_CHECK(d.D % 4 == 0, "q8 needs head_dim % 4 == 0");
+    TORCH_CHECK(d.H / d.Hkv <= 64, "q8 serves n_head / n_head_kv <= 64");
+    for (const torch::Tensor* t : {&k8, &v8})
+        TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->dim() == 1 &&
+                        t->scalar_type() == torch::kUInt8 &&
+                        t->numel() == (int64_t)d.slots * d.ctx * d.Ekv + 16,
+                    "k8/v8 must be flat u8 device tensors of "
+                    "n_slots*n_ctx*Ekv + 16 bytes");
+    for (const torch::Tensor* t : {&ksc, &vsc})
+        TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->dim() == 1 &&
+                        t->scalar_type() == torch::kFloat16 &&
+                        t->numel() == (int64_t)d.slots * d.ctx * d.Hkv,
+                    "k_scale/v_scale must be flat f16 device tensors of "
+                    "n_slots*n_ctx*Hkv");
+}
+
+// k_kv8_append: quantises row pos[t] of slot seq[t] of the f16 stages into
+// the byte stores and scale planes, in place
+void kv8_append(torch::Tensor k_stage, torch::Tensor v_stage,
+                torch::Tensor k8, torch::Tensor v8, torch::Tensor k_scale,
+                torch::Tensor v_scale, torch::Tensor pos, torch::Tensor seq,
+                int64_t n_head_kv, int64_t n_ctx, int64_t n_slots) {
+    TORCH_CHECK(n_head_kv >= 1 && n_ctx >= 1 && n_slots >= 1 &&
+                    k_stage.dim() == 1 && k_stage.numel() > 16 &&
+                    (k_stage.numel() - 16) % (n_head_kv * n_ctx * n_slots)
+                        == 0,
+                "k_stage must hold n_slots*n_ctx*Ekv + 16 halves");
+    const int64_t D = (k_stage.numel() - 16) / (n_head_kv * n_ctx * n_slots);
+    const AttnDims d = check_attn_args(pos.numel(), n_head_kv, n_head_kv, D,
+                                       n_ctx, n_slots, k_stage, v_stage, pos,
+                                       seq);
+    check_kv8_stores(d, k8, v8, k_scale, v_scale);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    launch_kv8_append(s, h16c(k_stage), h16c(v_stage),
+                      k8.data_ptr<uint8_t>(), v8.data_ptr<uint8_t>(),
+                      h16(k_scale), h16(v_scale), pos.data_ptr<int>(),
+                      seq.data_ptr<int>(), d.T, d.Hkv, d.D, d.ctx);
+}
+
+// k_attn_kv8 (+ k_attn_gqa_merge); the split-KV workspace is per call
+AttnResult attention_kv8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8,
+                         torch::Tensor k_scale, torch::Tensor v_scale,
+                         torch::Tensor pos, torch::Tensor seq,
+                         int64_t n_head, int64_t n_head_kv, int64_t n_ctx,
+                         int64_t n_slots) {
+    check_f32(q, "q");
+    TORCH_CHECK(q.dim() == 2 && q.size(0) >= 1, "q must be [T, E]");
+    TORCH_CHECK(n_head >= 1 && q.size(1) % n_head == 0,
+                "E not divisible by n_head");
+    const AttnDims d = check_attn_dims(q.size(0), n_head, n_head_kv,
+                                       q.size(1) / n_head, n_ctx, n_slots,
+                                       pos, seq);
+    check_kv8_stores(d, k8, v8, k_scale, v_scale);
+    AttnResult r = alloc_attn_result(d);
+    auto ws = torch::zeros(
+        {kv8_ws_numel(d.H, d.D, d.ctx)},
+        torch::TensorOptions().device(torch::kCUDA).dtype(torch::kFloat32));
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    launch_attn_kv8(s, q.data_ptr<float>(), k8.data_ptr<uint8_t>(),
+                    v8.data_ptr<uint8_t>(), h16c(k_scale), h16c(v_scale),
                     std::get<0>(r).data_ptr<float>(), u16p(std::get<1>(r)),
                     pos.data_ptr<int>(), seq.data_ptr<int>(), d.T, d.H,
                     d.Hkv, d.E, d.Ekv, d.D, d.ctx, ws.data_ptr<float>());
@@ -1223,6 +1372,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("seq"), py::arg("pfx"), py::arg("pslot"), py::arg("P"),
           py::arg("n_head"), py::arg("n_head_kv"), py::arg("n_ctx"),
           py::arg("n_slots"));
+    m.def("kv8_append", &kv8_append, py::arg("k_stage"), py::arg("v_stage"),
+          py::arg("k8"), py::arg("v8"), py::arg("k_scale"),
+          py::arg("v_scale"), py::arg("pos"), py::arg("seq"),
+          py::arg("n_head_kv"), py::arg("n_ctx"), py::arg("n_slots"));
+    m.def("attention_kv8", &attention_kv8, py::arg("q"), py::arg("k8"),
+          py::arg("v8"), py::arg("k_scale"), py::arg("v_scale"),
+          py::arg("pos"), py::arg("seq"), py::arg("n_head"),
+          py::arg("n_head_kv"), py::arg("n_ctx"), py::arg("n_slots"));
+    m.def("attn_kv8_chunk", [](int64_t n_ctx) {
+        return (int64_t)attn_kv8_chunk((int)n_ctx);
+    }, py::arg("n_ctx"));
+    m.def("attn_kv8_splits", [](int64_t n_ctx, int64_t T) {
+        return (int64_t)attn_kv8_splits((int)n_ctx, (int)T);
+    }, py::arg("n_ctx"), py::arg("T"));
     m.def("attn_prefix_chunk", [](int64_t n_ctx) {
         return (int64_t)attn_prefix_chunk((int)n_ctx);
     }, py::arg("n_ctx"));
@@ -1261,12 +1424,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "MI355X-native layer-slice inference engine (CDNA4 HIP kernels)";
     py::class_<SliceEngine, std::shared_ptr<SliceEngine>>(m, "SliceEngine")
         .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                      double, double, int64_t, int64_t, bool>(),
+                      double, double, int64_t, int64_t, bool, int64_t>(),
              py::arg("n_embd"), py::arg("n_head"), py::arg("n_layers"),
              py::arg("n_ff"), py::arg("n_ctx"), py::arg("max_batch"),
              py::arg("eps"), py::arg("rope_base"),
              py::arg("max_prefill") = 1024, py::arg("n_head_kv") = 0,
-             py::arg("gqa_attention") = true)
+             py::arg("gqa_attention") = true, py::arg("kv_dtype") = 0)
         .def("set_layer", &SliceEngine::set_layer)
         .def("set_extra", &SliceEngine::set_extra)
         .def("forward", &SliceEngine::forward, py::arg("x"),
@@ -1289,5 +1452,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def_property_readonly("n_ctx", &SliceEngine::n_ctx)
         .def_property_readonly("max_batch", &SliceEngine::max_batch)
         .def_property_readonly("k_cache", &SliceEngine::k_cache)
-        .def_property_readonly("v_cache", &SliceEngine::v_cache);
+        .def_property_readonly("v_cache", &SliceEngine::v_cache)
+        .def_property_readonly("k_scale", &SliceEngine::k_scale)
+        .def_property_readonly("v_scale", &SliceEngine::v_scale);
 }

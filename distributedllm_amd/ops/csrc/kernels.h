@@ -147,6 +147,49 @@ void launch_attn_gqa(hipStream_t s, const float* q_buf,
                      const int* seq, int T, int H, int Hkv, int E, int Ekv,
                      int D, int n_ctx, float* ws);
 
+// k_attn_gqa_merge alone: combines the ceil((pos[t] + 1) / chunk) partials
+// (m, l, o[D]) of every (token, head) in ws [T][H][S][D + 2] in split order;
+// tokens whose context fits one chunk are left alone. Shared by
+// launch_attn_gqa and launch_attn_kv8.
+void launch_attn_gqa_merge(hipStream_t s, const float* ws, float* out,
+                           unsigned short* out_prep, const int* pos, int T,
+                           int H, int E, int D, int jtw, int chunk, int S);
+
+// ------------------------------------------------ int8 KV cache (q8)
+// attention_kv8.hip. A cache row of one KV head is D re-biased bytes
+// u = q + 128, q in [-127, 127], and one f16 scale s = f16(amax / 127):
+// x ~ s * q. K and V caches: u8 [B, n_ctx, Ekv] per layer (+ 16 bytes of
+// tail pad on the whole allocation), scales f16 [B, n_ctx, Hkv]. D % 4 == 0.
+//   launch_kv8_append  k_kv8_append: quantises the T rows that the qkv
+//                      kernels wrote to the f16 stages [B, n_ctx, Ekv] at
+//                      (seq[t], pos[t]) into the byte caches and scale
+//                      planes; one wave per (token, KV head), K and V in
+//                      its two halves
+//   launch_attn_kv8    k_attn_kv8 (+ k_attn_gqa_merge): launch_attention's
+//                      semantics without the fused prologue, for every
+//                      1 <= H/Hkv <= 64 and every T, over the byte caches.
+//                      One block per (token, KV head, 16 query heads, KV
+//                      chunk) on the matrix cores. Splits follow the GQA
+//                      rule (functions of n_ctx alone for T <= 64, one
+//                      split for T > 64). ws: f32 [64][H][S][D + 2] with
+//                      S = attn_kv8_splits(n_ctx, 1); untouched when S = 1.
+int attn_kv8_chunk(int n_ctx);
+int attn_kv8_splits(int n_ctx, int T);
+
+void launch_kv8_append(hipStream_t s, const __half* k_stage,
+                       const __half* v_stage, uint8_t* k8_layer,
+                       uint8_t* v8_layer, __half* k_scale_layer,
+                       __half* v_scale_layer, const int* pos, const int* seq,
+                       int T, int Hkv, int D, int n_ctx);
+
+void launch_attn_kv8(hipStream_t s, const float* q_buf,
+                     const uint8_t* k8_layer, const uint8_t* v8_layer,
+                     const __half* k_scale_layer,
+                     const __half* v_scale_layer, float* out,
+                     unsigned short* out_prep, const int* pos,
+                     const int* seq, int T, int H, int Hkv, int E, int Ekv,
+                     int D, int n_ctx, float* ws);
+
 // ------------------------------------------------ shared-prefix attention
 // Token t attends rows [0, pfx[t]) of slot `pslot`, then rows
 // [pfx[t], pos[t]] of slot seq[t]. pfx is a device i32 [T] whose entries are

@@ -146,6 +146,10 @@ class ContinuousBatcher:
                     raise ValueError(
                         "shared_prefix needs an engine whose forward takes "
                         "prefix=")
+                if getattr(e, "kv_dtype", "f16") != "f16":
+                    raise ValueError(
+                        "shared_prefix and kv_dtype='q8' cannot be combined: "
+                        "shared-prefix attention reads an f16 KV cache")
                 n_ctx = getattr(e, "n_ctx", None)
                 if P < 1 or (n_ctx is not None and P >= n_ctx):
                     raise ValueError(
