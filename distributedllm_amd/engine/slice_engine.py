@@ -58,7 +58,8 @@ class HIPSliceEngine:
     def __init__(self, hp: ggml.Hparams, n_layers: int, first_layer: int,
                  n_ctx: int = 2048, max_batch: int = 16,
                  max_prefill: Optional[int] = None,
-                 gqa_attention: bool = True, kv_dtype: str = "f16"):
+                 gqa_attention: bool = True, kv_dtype: str = "f16",
+                 kv8_prefill: bool = True):
         from .. import ops
         core = ops.core()
         self.hp = hp
@@ -70,8 +71,11 @@ class HIPSliceEngine:
         # the (token, KV head) matrix-core kernel; False keeps k_attention
         self.gqa_attention = gqa_attention
         # "q8": int8 KV cache with one f16 scale per (row, KV head): half
-        # the KV bytes, every attention call on k_attn_kv8; no prefix=
+        # the KV bytes, attention on k_attn_kv8; no prefix=
         self.kv_dtype = _check_kv_dtype(kv_dtype)
+        # q8 prompt spans of more than 64 tokens in one call: the Q-tiled
+        # k_attn_kv8_prefill; False keeps k_attn_kv8 at every T
+        self.kv8_prefill = kv8_prefill
         # prefill token cap per forward call (side channels scale with it;
         # larger prompts tile host-side in max_prefill chunks)
         if max_prefill is None:
@@ -82,7 +86,7 @@ class HIPSliceEngine:
             eps=RMS_EPS, rope_base=ROPE_BASE, max_prefill=max_prefill,
             n_head_kv=hp.kv_heads if hp.is_gqa else 0,
             gqa_attention=gqa_attention,
-            kv_dtype=KV_DTYPES.index(kv_dtype))
+            kv_dtype=KV_DTYPES.index(kv_dtype), kv8_prefill=kv8_prefill)
         self.device = "cuda"
         self.has_extra = False
         # weight-tensor references for clone_shared (filled by .random()
@@ -94,11 +98,13 @@ class HIPSliceEngine:
     @classmethod
     def from_ggml(cls, f: ggml.GGMLFile, n_ctx: int = 2048,
                   max_batch: int = 16, gqa_attention: bool = True,
-                  kv_dtype: str = "f16") -> "HIPSliceEngine":
+                  kv_dtype: str = "f16",
+                  kv8_prefill: bool = True) -> "HIPSliceEngine":
         hp = f.hparams
         first = hp.first_layer if hp.first_layer is not None else 0
         eng = cls(hp, hp.n_layer, first, n_ctx, max_batch,
-                  gqa_attention=gqa_attention, kv_dtype=kv_dtype)
+                  gqa_attention=gqa_attention, kv_dtype=kv_dtype,
+                  kv8_prefill=kv8_prefill)
         eng.load_layers(f)
         return eng
 
@@ -107,8 +113,8 @@ class HIPSliceEngine:
                n_ctx: int = 2048, max_batch: int = 16, seed: int = 0,
                with_extra: bool = True,
                max_prefill: Optional[int] = None,
-               gqa_attention: bool = True,
-               kv_dtype: str = "f16") -> "HIPSliceEngine":
+               gqa_attention: bool = True, kv_dtype: str = "f16",
+               kv8_prefill: bool = True) -> "HIPSliceEngine":
         """Random-init engine straight on the GPU (synthetic benchmarking).
 
         Generates weights directly in the repacked kernel layout — identical
@@ -117,7 +123,7 @@ class HIPSliceEngine:
         """
         eng = cls(hp, n_layers, first_layer, n_ctx, max_batch,
                   max_prefill=max_prefill, gqa_attention=gqa_attention,
-                  kv_dtype=kv_dtype)
+                  kv_dtype=kv_dtype, kv8_prefill=kv8_prefill)
         g = torch.Generator(device="cuda")
         g.manual_seed(seed)
         E, F, V = hp.n_embd, hp.n_ff, hp.n_vocab
@@ -185,7 +191,8 @@ class HIPSliceEngine:
                               self.n_ctx, self.max_batch,
                               max_prefill=int(self._eng.max_prefill),
                               gqa_attention=self.gqa_attention,
-                              kv_dtype=self.kv_dtype)
+                              kv_dtype=self.kv_dtype,
+                              kv8_prefill=self.kv8_prefill)
         for li, (an, fn, mats) in enumerate(self._layers_cache):
             twin._eng.set_layer(li, an, fn, mats)
         twin._layers_cache = self._layers_cache  # enables further clones

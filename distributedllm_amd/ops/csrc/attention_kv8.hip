@@ -1,6 +1,7 @@
 // Int8 KV cache (kv_dtype = "q8", gfx950): the quantising append
-// `k_kv8_append` and the matrix-core attention kernel `k_attn_kv8` over the
-// byte caches, with their launchers (formats and semantics: kernels.h).
+// `k_kv8_append`, the matrix-core attention kernel `k_attn_kv8` over the
+// byte caches and its Q-tiled prefill sibling `k_attn_kv8_prefill`, with
+// their launchers (formats and semantics: kernels.h).
 //
 // A cache row of one KV head is D bytes u = q + 128, q in [-127, 127], and
 // one f16 scale s: x ~ s * q. 0x6400 | u is exactly the f16 value 1024 + u
@@ -471,6 +472,302 @@ GQA_FN __global__ __launch_bounds__(BLOCK) void k_attn_kv8(
     }
 }
 
+// ----------------------------------------------------- prefill attention
+// k_attn_kv8_prefill: k_attn_kv8 with the consumers of a KV row changed, the
+// step k_attn_prefix made from k_attn_gqa. One block per (16-query tile,
+// query head), grid (ceil(T/16), H): the 16 MFMA columns are the tile's 16
+// queries for one head, so a KV row is read and expanded from bytes once per
+// 16 queries, not once per query. No split-KV, no workspace: prefill
+// launches are wide. The tile's same-seq segments are walked as in
+// k_attn_prefill_mfma: for a segment the block streams rows [0, jmax + 1) of
+// its slot with the loop of k_attn_kv8 (Kv8Tile, kv8_load_tile, kv8_stage_v,
+// kv8_expand4 as they are), and score slot (row j, column c) is live iff
+// j < lim[c], lim = pos + 1 for a column of the segment and 0 for any other.
+//
+// The running state (m, l, R) is per column, and "the wave's first tile has
+// an attended row" does not hold per column: a column can be outside the
+// segment, past T, or have every row of this wave's tiles above its pos.
+// Such a column is `dead` (m_new = -inf): p = 0, alpha = 1, R stays 0, so it
+// keeps (m = -inf, l = 0, o = 0) and no -inf - -inf is ever formed. A tile
+// that is masked for a column that has state leaves that state bit for bit:
+// tm = -inf and svm = 0 give m_new = m, R_new = R, alpha = expf(0) = 1 and
+// P~ = 0. R is the running maximum of the V scales over the rows the COLUMN
+// attends, carried like m, so P~ = p * s_v / R <= 1 per token and a token's
+// bits do not depend on its tile mates. Row 0 is attended by every token and
+// belongs to wave 0's first tile, so the merge sees l > 0 for every t < T.
+
+// kv8_tile_step with a per-column row limit and dead-column handling
+template <int DC, int NSC>
+GQA_FN __device__ __forceinline__ void kv8_tile_step_q(
+    const Kv8Tile<NSC>& tile, const ABFrag (&qf)[2 * NSC], uint32_t* vt,
+    _Float16* st, int tj, int lim, int lane, float qk_scale, float& m,
+    float& l, float& R, f32x4 (&oacc)[DC]) {
+    const int lq = lane & 15;
+    const int lg = lane >> 4;
+    f32x4 sc[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        sc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < NSC; ++c) {
+            ABFrag ka, kb;
+            kv8_expand4(tile.k[r][c][0], ka.u[0], ka.u[1]);
+            kv8_expand4(tile.k[r][c][1], ka.u[2], ka.u[3]);
+            kv8_expand4(tile.k[r][c][2], kb.u[0], kb.u[1]);
+            kv8_expand4(tile.k[r][c][3], kb.u[2], kb.u[3]);
+            sc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                ka.v, qf[2 * c].v, sc[r], 0, 0, 0);
+            sc[r] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                kb.v, qf[2 * c + 1].v, sc[r], 0, 0, 0);
+        }
+    }
+    reinterpret_cast<unsigned short*>(st)[lane] = tile.sc;
+    kv8_stage_v(vt, tile.v, lane);
+    gqa_wave_sync();                        // scales, V tile written -> read
+
+    // lane holds s[j = tj + r*16 + lg*4 + jj][column lq] as slot r*4 + jj
+    float s[8], sv[8], tm = -INFINITY, svm = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const kv8_f16x4 ks =
+            *reinterpret_cast<const kv8_f16x4*>(st + r * 16 + lg * 4);
+        const kv8_f16x4 vs =
+            *reinterpret_cast<const kv8_f16x4*>(st + 32 + r * 16 + lg * 4);
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const bool ok = tj + r * 16 + lg * 4 + jj < lim;
+            s[r * 4 + jj] = ok ? sc[r][jj] * ((float)ks[jj] * qk_scale)
+                               : -INFINITY;
+            sv[r * 4 + jj] = ok ? (float)vs[jj] : 0.0f;
+            tm = fmaxf(tm, s[r * 4 + jj]);
+            svm = fmaxf(svm, sv[r * 4 + jj]);
+        }
+    }
+    tm = fmaxf(tm, gqa_shfl_xor(tm, lane, 16));
+    tm = fmaxf(tm, gqa_shfl_xor(tm, lane, 32));
+    // a tile above every column's limit (the odd tile past the segment end):
+    // wave-uniform skip, nothing changes
+    if (__builtin_amdgcn_ballot_w64(tm != -INFINITY) == 0) {
+        gqa_wave_sync();                    // read -> next tile's write
+        return;
+    }
+    svm = fmaxf(svm, gqa_shfl_xor(svm, lane, 16));
+    svm = fmaxf(svm, gqa_shfl_xor(svm, lane, 32));
+    const float m_new = fmaxf(m, tm);
+    const float R_new = fmaxf(R, svm);
+    const bool dead = m_new == -INFINITY;   // column has attended no row yet
+    const float inv_r = (R_new > 0.0f) ? __builtin_amdgcn_rcpf(R_new) : 0.0f;
+    // m = -inf: l = 0 and oacc = 0, any finite factor will do; 1 keeps a
+    // dead column out of the rescale below
+    const float alpha = (m == -INFINITY) ? (dead ? 1.0f : 0.0f)
+                                         : __expf(m - m_new);
+    // accumulators are in units of R: exactly 1 while R stands
+    const float alpha_o = alpha * ((R_new == R) ? 1.0f : R * inv_r);
+    float ts = 0.0f, pt[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float p = dead ? 0.0f : __expf(s[e] - m_new);  // 0 if masked
+        ts += p;
+        pt[e] = p * (sv[e] * inv_r);            // P~ in [0, 1]
+    }
+    ABFrag p;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        p.u[i] = gqa_pack_f16(pt[2 * i], pt[2 * i + 1]);
+    ts += gqa_shfl_xor(ts, lane, 16);
+    ts += gqa_shfl_xor(ts, lane, 32);
+    l = l * alpha + ts;
+    m = m_new;
+    R = R_new;
+
+    // wave-uniform branch; x * 1 is x, so a column whose factor is 1 keeps
+    // its bits whatever the other columns do
+    if (__builtin_amdgcn_ballot_w64(alpha_o != 1.0f) != 0) {
+#pragma unroll
+        for (int dc = 0; dc < DC; ++dc) {
+            oacc[dc][0] *= alpha_o; oacc[dc][1] *= alpha_o;
+            oacc[dc][2] *= alpha_o; oacc[dc][3] *= alpha_o;
+        }
+    }
+#pragma unroll
+    for (int dc = 0; dc < DC; ++dc) {
+        ABFrag vf;
+        kv8_expand4(vt[lg * KV8_VSTRIDE + dc * 16 + lq], vf.u[0], vf.u[1]);
+        kv8_expand4(vt[(4 + lg) * KV8_VSTRIDE + dc * 16 + lq], vf.u[2],
+                    vf.u[3]);
+        oacc[dc] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf.v, p.v,
+                                                          oacc[dc], 0, 0, 0);
+    }
+    gqa_wave_sync();                        // read -> next tile's write
+}
+
+int attn_kv8_route(int T, int decode, int kv8_prefill) {
+    return (T > 64 && !decode && kv8_prefill) ? 1 : 0;
+}
+
+template <int DC>
+GQA_FN __global__ __launch_bounds__(BLOCK) void k_attn_kv8_prefill(
+    const float* __restrict__ q_buf, const uint8_t* __restrict__ k8,
+    const uint8_t* __restrict__ v8, const __half* __restrict__ k_scale,
+    const __half* __restrict__ v_scale, float* __restrict__ out,
+    unsigned short* __restrict__ out_prep, const int* __restrict__ pos,
+    const int* __restrict__ seq, int T, int grp, int E, int Ekv, int D,
+    int n_ctx, int jtw) {
+    constexpr int NSC = DC > 4 ? DC / 4 : 1;
+    constexpr int QW = NSC * 64;        // staged q row, halves
+    const int t0 = (int)blockIdx.x * 16;
+    const int h = blockIdx.y;
+    const int hk = h / grp;             // GQA kv head
+    const int nq = min(16, T - t0);
+    const int Hkv = Ekv / D;
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = __builtin_amdgcn_readfirstlane(tid / WAVE);  // scalar
+    const int lq = lane & 15;
+    const int lg = lane >> 4;
+
+    // LDS as in k_attn_kv8: the waves' V tiles and scales and the staged Q
+    // while streaming, the waves' O partials [w][col][OSTR] after it
+    constexpr int OSTR = DC * 16 + 4;
+    constexpr int VT_BYTES = NWAVES * 8 * KV8_VSTRIDE * (int)sizeof(uint32_t);
+    constexpr int SC_BYTES = NWAVES * 64 * (int)sizeof(_Float16);
+    constexpr int Q_BYTES = 16 * (QW + 8) * (int)sizeof(_Float16);
+    constexpr int O_BYTES = NWAVES * 16 * OSTR * (int)sizeof(float);
+    constexpr int S_BYTES = VT_BYTES + SC_BYTES + Q_BYTES;
+    constexpr int LDS_BYTES = S_BYTES > O_BYTES ? S_BYTES : O_BYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
+    __shared__ float lds_m[NWAVES][16];
+    __shared__ float lds_l[NWAVES][16];
+    __shared__ int lds_pos[16];
+    __shared__ int lds_seq[16];         // -1 past T
+    uint32_t* vt = reinterpret_cast<uint32_t*>(lds_raw) +
+                   wid * 8 * KV8_VSTRIDE;
+    _Float16* st = reinterpret_cast<_Float16*>(lds_raw + VT_BYTES) + wid * 64;
+    _Float16 (*lds_q)[QW + 8] = reinterpret_cast<_Float16 (*)[QW + 8]>(
+        lds_raw + VT_BYTES + SC_BYTES);
+    float* lds_o = reinterpret_cast<float*>(lds_raw);
+
+    if (tid < 16) {
+        const bool ok = tid < nq;
+        lds_pos[tid] = ok ? pos[t0 + (ok ? tid : 0)] : 0;
+        lds_seq[tid] = ok ? seq[t0 + (ok ? tid : 0)] : -1;
+    }
+    // Q tile -> LDS as plain f16, zero past D and past T (the factor does
+    // the masking). 1/sqrt(D) joins the K scale.
+    {
+        const float* qt = q_buf + (size_t)t0 * E + (size_t)h * D;
+#pragma unroll
+        for (int i = 0; i < 16 * QW / BLOCK; ++i) {
+            const int idx = tid + i * BLOCK;
+            const int col = idx / QW;
+            const int d = idx % QW;
+            const bool ok = col < nq && d < D;
+            const float v = qt[ok ? (size_t)col * E + d : 0] *
+                            (ok ? 1.0f : 0.0f);
+            lds_q[col][d] = (_Float16)v;
+        }
+    }
+    gqa_block_sync();
+    // score-MFMA B fragments in k_attn_kv8's permuted contraction order:
+    // lane (column lq, lg) holds d = c*64 + lg*16 + 0..7 for the first MFMA
+    // of chunk c and + 8..15 for the second
+    ABFrag qf[2 * NSC];
+#pragma unroll
+    for (int c = 0; c < 2 * NSC; ++c) {
+        const uint4 u = *reinterpret_cast<const uint4*>(
+            &lds_q[lq][(c >> 1) * 64 + lg * 16 + (c & 1) * 8]);
+        qf[c].u[0] = u.x; qf[c].u[1] = u.y;
+        qf[c].u[2] = u.z; qf[c].u[3] = u.w;
+    }
+    const float qk_scale = rsqrtf((float)D);
+    const int pos_q = lds_pos[lq];
+
+    float m = -INFINITY, l = 0.0f;      // running state of column lq
+    float R = 0.0f;                     // running max of its rows' V scales
+    f32x4 oacc[DC];
+#pragma unroll
+    for (int dc = 0; dc < DC; ++dc) oacc[dc] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    constexpr int STEP = NWAVES * 32;
+    int a = 0;
+    while (a < nq) {                    // same-seq segments, block-uniform
+        const int sseq = __builtin_amdgcn_readfirstlane(lds_seq[a]);
+        int b = a + 1;
+        while (b < nq && __builtin_amdgcn_readfirstlane(lds_seq[b]) == sseq)
+            ++b;
+        int jmax = 0;
+        for (int c = a; c < b; ++c)
+            jmax = max(jmax, __builtin_amdgcn_readfirstlane(lds_pos[c]));
+        const int J = jmax + 1;         // rows streamed: [0, J) of slot sseq
+        const int lim = (lq >= a && lq < b) ? pos_q + 1 : 0;
+        const size_t row0 = (size_t)sseq * n_ctx;
+        const uint8_t* kb = k8 + row0 * Ekv + hk * D;
+        const uint8_t* vb = v8 + row0 * Ekv + hk * D;
+        const unsigned short* ksb =
+            reinterpret_cast<const unsigned short*>(k_scale) + row0 * Hkv +
+            hk;
+        const unsigned short* vsb =
+            reinterpret_cast<const unsigned short*>(v_scale) + row0 * Hkv +
+            hk;
+        // k_attn_kv8's loop: wave w streams tiles w, w+4, ..., two per
+        // iteration in two buffers, loads one tile ahead; rows at or past J
+        // read row 0 and are above every lim
+        int tj = wid * 32;
+        if (tj < J) {                   // wave-uniform, scalar
+            Kv8Tile<NSC> cur, alt;
+            kv8_load_tile(cur, kb, vb, ksb, vsb, tj, J, Ekv, Hkv, D, lane);
+            do {
+                kv8_load_tile(alt, kb, vb, ksb, vsb, tj + STEP, J, Ekv, Hkv,
+                              D, lane);
+                kv8_tile_step_q<DC, NSC>(cur, qf, vt, st, tj, lim, lane,
+                                         qk_scale, m, l, R, oacc);
+                kv8_load_tile(cur, kb, vb, ksb, vsb, tj + 2 * STEP, J, Ekv,
+                              Hkv, D, lane);
+                kv8_tile_step_q<DC, NSC>(alt, qf, vt, st, tj + STEP, lim,
+                                         lane, qk_scale, m, l, R, oacc);
+                tj += 2 * STEP;
+            } while (tj < J);
+        }
+        a = b;
+    }
+    gqa_block_sync();                   // tiles and Q are dead: reuse LDS
+
+    // merge the 4 waves' partials in wave order (lane group 0 holds the
+    // column's (m, l); oacc[dc][jj] * R is O[d = dc*16 + lg*4 + jj][col lq])
+    if (lg == 0) {
+        lds_m[wid][lq] = m;
+        lds_l[wid][lq] = l;
+    }
+#pragma unroll
+    for (int dc = 0; dc < DC; ++dc) {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+            lds_o[(wid * 16 + lq) * OSTR + dc * 16 + lg * 4 + jj] =
+                oacc[dc][jj] * R;
+    }
+    gqa_block_sync();
+    const int col = tid >> 4;
+    if (col >= nq) return;
+    float mstar = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) mstar = fmaxf(mstar, lds_m[w][col]);
+    float wsc[NWAVES], lstar = 0.0f;
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) {
+        const float mw = lds_m[w][col];         // -inf: no row of this wave
+        wsc[w] = (mw == -INFINITY) ? 0.0f : __expf(mw - mstar);
+        lstar += lds_l[w][col] * wsc[w];
+    }
+    for (int d = tid & 15; d < D; d += 16) {
+        float ostar = 0.0f;
+#pragma unroll
+        for (int w = 0; w < NWAVES; ++w)
+            ostar += lds_o[(w * 16 + col) * OSTR + d] * wsc[w];
+        gqa_store_out(ostar / lstar, h * D + d, t0 + col, E, jtw, out,
+                      out_prep);
+    }
+}
+
 // ============================================================== launchers
 
 void launch_kv8_append(hipStream_t s, const __half* k_stage,
@@ -506,4 +803,20 @@ void launch_attn_kv8(hipStream_t s, const float* q_buf,
     if (S > 1)
         launch_attn_gqa_merge(s, ws, out, out_prep, pos, T, H, E, D, jtw,
                               chunk, S);
+}
+
+void launch_attn_kv8_prefill(hipStream_t s, const float* q_buf,
+                             const uint8_t* k8_layer, const uint8_t* v8_layer,
+                             const __half* k_scale_layer,
+                             const __half* v_scale_layer, float* out,
+                             unsigned short* out_prep, const int* pos,
+                             const int* seq, int T, int H, int Hkv, int E,
+                             int Ekv, int D, int n_ctx) {
+    auto kern = D <= 16 ? k_attn_kv8_prefill<1>
+              : D <= 32 ? k_attn_kv8_prefill<2>
+              : D <= 64 ? k_attn_kv8_prefill<4> : k_attn_kv8_prefill<8>;
+    hipLaunchKernelGGL(kern, dim3((T + 15) / 16, H), dim3(BLOCK), 0, s, q_buf,
+                       k8_layer, v8_layer, k_scale_layer, v_scale_layer, out,
+                       out_prep, pos, seq, T, H / Hkv, E, Ekv, D, n_ctx,
+                       jt_width(T));
 }

@@ -192,7 +192,7 @@ class SliceEngine {
                 int64_t n_ff, int64_t n_ctx, int64_t max_batch, double eps,
                 double rope_base, int64_t max_prefill = 1024,
                 int64_t n_head_kv = 0, bool gqa_attention = true,
-                int64_t kv_dtype = 0)
+                int64_t kv_dtype = 0, bool kv8_prefill = true)
         : E_((int)n_embd),
           H_((int)n_head),
           D_((int)(n_embd / n_head)),
@@ -202,7 +202,8 @@ class SliceEngine {
           B_((int)max_batch),
           eps_((float)eps),
           gqa_attention_(gqa_attention),
-          kv8_(kv_dtype == 1) {
+          kv8_(kv_dtype == 1),
+          kv8_prefill_(kv8_prefill) {
         TORCH_CHECK(kv_dtype == 0 || kv_dtype == 1,
                     "kv_dtype must be 0 (f16) or 1 (q8)");
         TORCH_CHECK(E_ % H_ == 0, "n_embd not divisible by n_head");
@@ -496,7 +497,8 @@ class SliceEngine {
             // run every such call on the (token, KV head) MFMA kernel
             if (kv8_) {
                 // every T: quantise the rows just staged, then attend over
-                // the layer's byte cache
+                // the layer's byte cache, prompt spans of more than 64
+                // tokens on the Q-tiled kernel
                 uint8_t* k8 = k_cache_.data_ptr<uint8_t>() +
                               (size_t)li * layer_stride;
                 uint8_t* v8 = v_cache_.data_ptr<uint8_t>() +
@@ -509,9 +511,14 @@ class SliceEngine {
                 launch_kv8_append(s, kc, vc, k8, v8, ksc, vsc, pp, sp, T,
                                   HK_, D_, ctx_);
                 ck("kv8 append", li);
-                launch_attn_kv8(s, qb, k8, v8, ksc, vsc, ab, aprep, pp, sp,
-                                T, H_, HK_, E_, EK_, D_, ctx_,
-                                kv8_ws_.data_ptr<float>());
+                if (attn_kv8_route(T, decode ? 1 : 0, kv8_prefill_ ? 1 : 0))
+                    launch_attn_kv8_prefill(s, qb, k8, v8, ksc, vsc, ab,
+                                            aprep, pp, sp, T, H_, HK_, E_,
+                                            EK_, D_, ctx_);
+                else
+                    launch_attn_kv8(s, qb, k8, v8, ksc, vsc, ab, aprep, pp,
+                                    sp, T, H_, HK_, E_, EK_, D_, ctx_,
+                                    kv8_ws_.data_ptr<float>());
             } else if (shared) {
                 launch_attn_prefix(s, qb, kc, vc, ab, aprep, pp, sp, fp,
                                    pslot, plen, T, H_, HK_, E_, EK_, D_,
@@ -779,6 +786,7 @@ class SliceEngine {
     float eps_;
     bool gqa_attention_;     // GQA models: route attention to k_attn_gqa
     bool kv8_;               // kv_dtype q8: byte caches, k_attn_kv8
+    bool kv8_prefill_;       // q8 prompt spans > 64: k_attn_kv8_prefill
     std::vector<Layer> layers_;
     std::vector<bool> loaded_;
     torch::Tensor kv_store_k_, kv_store_v_;
@@ -991,12 +999,13 @@ void kv8_append(torch::Tensor k_stage, torch::Tensor v_stage,
                       seq.data_ptr<int>(), d.T, d.Hkv, d.D, d.ctx);
 }
 
-// k_attn_kv8 (+ k_attn_gqa_merge); the split-KV workspace is per call
-AttnResult attention_kv8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8,
-                         torch::Tensor k_scale, torch::Tensor v_scale,
-                         torch::Tensor pos, torch::Tensor seq,
-                         int64_t n_head, int64_t n_head_kv, int64_t n_ctx,
-                         int64_t n_slots) {
+// the arguments the two q8 attention hooks share
+AttnDims check_kv8_args(const torch::Tensor& q, const torch::Tensor& k8,
+                        const torch::Tensor& v8, const torch::Tensor& k_scale,
+                        const torch::Tensor& v_scale,
+                        const torch::Tensor& pos, const torch::Tensor& seq,
+                        int64_t n_head, int64_t n_head_kv, int64_t n_ctx,
+                        int64_t n_slots) {
     check_f32(q, "q");
     TORCH_CHECK(q.dim() == 2 && q.size(0) >= 1, "q must be [T, E]");
     TORCH_CHECK(n_head >= 1 && q.size(1) % n_head == 0,
@@ -1005,6 +1014,17 @@ AttnResult attention_kv8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8,
                                        q.size(1) / n_head, n_ctx, n_slots,
                                        pos, seq);
     check_kv8_stores(d, k8, v8, k_scale, v_scale);
+    return d;
+}
+
+// k_attn_kv8 (+ k_attn_gqa_merge); the split-KV workspace is per call
+AttnResult attention_kv8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8,
+                         torch::Tensor k_scale, torch::Tensor v_scale,
+                         torch::Tensor pos, torch::Tensor seq,
+                         int64_t n_head, int64_t n_head_kv, int64_t n_ctx,
+                         int64_t n_slots) {
+    const AttnDims d = check_kv8_args(q, k8, v8, k_scale, v_scale, pos, seq,
+                                      n_head, n_head_kv, n_ctx, n_slots);
     AttnResult r = alloc_attn_result(d);
     auto ws = torch::zeros(
         {kv8_ws_numel(d.H, d.D, d.ctx)},
@@ -1015,6 +1035,26 @@ AttnResult attention_kv8(torch::Tensor q, torch::Tensor k8, torch::Tensor v8,
                     std::get<0>(r).data_ptr<float>(), u16p(std::get<1>(r)),
                     pos.data_ptr<int>(), seq.data_ptr<int>(), d.T, d.H,
                     d.Hkv, d.E, d.Ekv, d.D, d.ctx, ws.data_ptr<float>());
+    return r;
+}
+
+// k_attn_kv8_prefill at any T >= 1 (the engine runs it at T > 64)
+AttnResult attention_kv8_prefill(torch::Tensor q, torch::Tensor k8,
+                                 torch::Tensor v8, torch::Tensor k_scale,
+                                 torch::Tensor v_scale, torch::Tensor pos,
+                                 torch::Tensor seq, int64_t n_head,
+                                 int64_t n_head_kv, int64_t n_ctx,
+                                 int64_t n_slots) {
+    const AttnDims d = check_kv8_args(q, k8, v8, k_scale, v_scale, pos, seq,
+                                      n_head, n_head_kv, n_ctx, n_slots);
+    AttnResult r = alloc_attn_result(d);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    launch_attn_kv8_prefill(s, q.data_ptr<float>(), k8.data_ptr<uint8_t>(),
+                            v8.data_ptr<uint8_t>(), h16c(k_scale),
+                            h16c(v_scale), std::get<0>(r).data_ptr<float>(),
+                            u16p(std::get<1>(r)), pos.data_ptr<int>(),
+                            seq.data_ptr<int>(), d.T, d.H, d.Hkv, d.E, d.Ekv,
+                            d.D, d.ctx);
     return r;
 }
 
@@ -1380,6 +1420,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("v8"), py::arg("k_scale"), py::arg("v_scale"),
           py::arg("pos"), py::arg("seq"), py::arg("n_head"),
           py::arg("n_head_kv"), py::arg("n_ctx"), py::arg("n_slots"));
+    m.def("attention_kv8_prefill", &attention_kv8_prefill, py::arg("q"),
+          py::arg("k8"), py::arg("v8"), py::arg("k_scale"),
+          py::arg("v_scale"), py::arg("pos"), py::arg("seq"),
+          py::arg("n_head"), py::arg("n_head_kv"), py::arg("n_ctx"),
+          py::arg("n_slots"));
+    m.def("attn_kv8_route", [](int64_t T, bool decode, bool kv8_prefill) {
+        return (int64_t)attn_kv8_route((int)T, decode ? 1 : 0,
+                                       kv8_prefill ? 1 : 0);
+    }, py::arg("T"), py::arg("decode"), py::arg("kv8_prefill"));
     m.def("attn_kv8_chunk", [](int64_t n_ctx) {
         return (int64_t)attn_kv8_chunk((int)n_ctx);
     }, py::arg("n_ctx"));
@@ -1424,12 +1473,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "MI355X-native layer-slice inference engine (CDNA4 HIP kernels)";
     py::class_<SliceEngine, std::shared_ptr<SliceEngine>>(m, "SliceEngine")
         .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                      double, double, int64_t, int64_t, bool, int64_t>(),
+                      double, double, int64_t, int64_t, bool, int64_t,
+                      bool>(),
              py::arg("n_embd"), py::arg("n_head"), py::arg("n_layers"),
              py::arg("n_ff"), py::arg("n_ctx"), py::arg("max_batch"),
              py::arg("eps"), py::arg("rope_base"),
              py::arg("max_prefill") = 1024, py::arg("n_head_kv") = 0,
-             py::arg("gqa_attention") = true, py::arg("kv_dtype") = 0)
+             py::arg("gqa_attention") = true, py::arg("kv_dtype") = 0,
+             py::arg("kv8_prefill") = true)
         .def("set_layer", &SliceEngine::set_layer)
         .def("set_extra", &SliceEngine::set_extra)
         .def("forward", &SliceEngine::forward, py::arg("x"),

@@ -173,8 +173,20 @@ void launch_attn_gqa_merge(hipStream_t s, const float* ws, float* out,
 //                      rule (functions of n_ctx alone for T <= 64, one
 //                      split for T > 64). ws: f32 [64][H][S][D + 2] with
 //                      S = attn_kv8_splits(n_ctx, 1); untouched when S = 1.
+//   launch_attn_kv8_prefill  k_attn_kv8_prefill: launch_attn_prefill's
+//                      semantics over the byte caches, any T >= 1 and any
+//                      1 <= H/Hkv <= 64. One block per (16-query tile, query
+//                      head), the tile's queries as the MFMA columns: a K/V
+//                      row is read and expanded once per 16 queries.
+//                      Mixed-seq tiles segment internally; running max, sum
+//                      and V-scale maximum are per query, so a token's bits
+//                      do not depend on its tile mates. No split, no ws.
+//   attn_kv8_route     which of the two the engine runs: 1 (Q-tiled) iff
+//                      T > 64, not decode and kv8_prefill; else 0
+//                      (launch_attn_kv8, wide decode included)
 int attn_kv8_chunk(int n_ctx);
 int attn_kv8_splits(int n_ctx, int T);
+int attn_kv8_route(int T, int decode, int kv8_prefill);
 
 void launch_kv8_append(hipStream_t s, const __half* k_stage,
                        const __half* v_stage, uint8_t* k8_layer,
@@ -189,6 +201,14 @@ void launch_attn_kv8(hipStream_t s, const float* q_buf,
                      unsigned short* out_prep, const int* pos,
                      const int* seq, int T, int H, int Hkv, int E, int Ekv,
                      int D, int n_ctx, float* ws);
+
+void launch_attn_kv8_prefill(hipStream_t s, const float* q_buf,
+                             const uint8_t* k8_layer, const uint8_t* v8_layer,
+                             const __half* k_scale_layer,
+                             const __half* v_scale_layer, float* out,
+                             unsigned short* out_prep, const int* pos,
+                             const int* seq, int T, int H, int Hkv, int E,
+                             int Ekv, int D, int n_ctx);
 
 // ------------------------------------------------ shared-prefix attention
 // Token t attends rows [0, pfx[t]) of slot `pslot`, then rows

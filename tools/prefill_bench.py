@@ -30,14 +30,21 @@ def main():
     ap.add_argument("--streams", type=int, default=1,
                     help="concatenated same-length prompts of distinct "
                          "sequences in ONE call (mixed admission stream)")
+    ap.add_argument("--kv-dtype", default="f16", choices=["f16", "q8"])
+    ap.add_argument("--no-kv8-prefill", action="store_true",
+                    help="q8: keep the per-token k_attn_kv8 at T > 64")
+    ap.add_argument("--layers", type=int, default=0,
+                    help="build only the first N layers (0: the preset's)")
     args = ap.parse_args()
     p = PRESETS[args.model]
     hp = p.hparams(FTYPES[args.ftype])
     spans = [int(s) for s in args.spans.split(",")]
     ctx = max(spans)
-    eng = HIPSliceEngine.random(hp, n_layers=p.n_layer, n_ctx=ctx,
-                                max_batch=max(args.streams, 1), seed=0,
-                                with_extra=True, max_prefill=ctx)
+    eng = HIPSliceEngine.random(hp, n_layers=args.layers or p.n_layer,
+                                n_ctx=ctx, max_batch=max(args.streams, 1),
+                                seed=0, with_extra=True, max_prefill=ctx,
+                                kv_dtype=args.kv_dtype,
+                                kv8_prefill=not args.no_kv8_prefill)
     g = torch.Generator(device="cuda")
     g.manual_seed(1)
     for S in spans:
@@ -60,7 +67,9 @@ def main():
             "span": S, "streams": args.streams,
             "prefill_tok_s": round(S * args.streams / dt, 1),
             "ms": round(dt * 1e3, 2), "ftype": args.ftype,
-            "model": p.name}), flush=True)
+            "model": p.name, "layers": args.layers or p.n_layer,
+            "kv_dtype": args.kv_dtype,
+            "kv8_prefill": not args.no_kv8_prefill}), flush=True)
 
 
 if __name__ == "__main__":
