@@ -450,10 +450,15 @@ class SliceEngine {
         unsigned short* gprep = u16p(gprep_);
         float* ssa = ss_attn_.data_ptr<float>();
         float* ssf = ss_ffn_.data_ptr<float>();
-        // zero the atomic sumsq slots, then stage x into the side channel
+        // zero the atomic sumsq slots, then stage x into the side channel.
+        // Every xprep is written for its reader: the producer multiplies in
+        // the norm weights of the NORM kernel that consumes it (layer 0's
+        // attention norm here, ffn_normprep after wo, the next layer's
+        // attention norm after w2)
         (void)hipMemsetAsync(ssa, 0, sizeof(float) * (L_ + 1) * ssw_, s);
         (void)hipMemsetAsync(ssf, 0, sizeof(float) * L_ * ssw_, s);
-        launch_prep_x(s, xp, xprep, ssa, E_, T, jt_width(T));
+        launch_prep_x(s, xp, xprep, ssa, E_, T, jt_width(T),
+                      u16p(layers_[0].attn_normprep));
         // One layer loop for every T, sequenced here in C++ — no host
         // tiling, no library GEMMs, q4 tiles read directly. The launchers
         // pick decode or large-M kernels by T; large-M (more than 64 tokens)
@@ -485,9 +490,8 @@ class SliceEngine {
             // the GQA and q8 kernels have no fused prologue: k_qkv_finish
             // runs
             const int slab_used = launch_qkv16(
-                s, l.mq.w, l.mk.w, l.mv.w, xprep, u16p(l.attn_normprep),
-                ssa + li * ssw_, eps_, qb, kc, vc, pp, sp, ifr, E_, EK_,
-                D_, ctx_, T, slab,
+                s, l.mq.w, l.mk.w, l.mv.w, xprep, ssa + li * ssw_, eps_,
+                qb, kc, vc, pp, sp, ifr, E_, EK_, D_, ctx_, T, slab,
                 /*skip_finish=*/
                 (decode && route != 2 && !shared && !kv8_) ? 1 : 0);
             ck("qkv", li);
@@ -538,13 +542,17 @@ class SliceEngine {
             }
             ck("attn", li);
             launch_gemm16_residual(s, l.mo.w, aprep, xp, xprep,
-                                   ssf + li * ssw_, T, slab, split_ok);
+                                   ssf + li * ssw_, T, slab, split_ok,
+                                   u16p(l.ffn_normprep));
             ck("wo", li);
-            launch_ffn16(s, l.m1.w, l.m3.w, xprep, u16p(l.ffn_normprep),
-                         ssf + li * ssw_, eps_, gprep, T);
+            launch_ffn16(s, l.m1.w, l.m3.w, xprep, ssf + li * ssw_, eps_,
+                         gprep, T);
             ck("ffn", li);
-            launch_gemm16_residual(s, l.m2.w, gprep, xp, xprep,
-                                   ssa + (li + 1) * ssw_, T, slab, split_ok);
+            // the last layer's xprep has no reader in this engine
+            launch_gemm16_residual(
+                s, l.m2.w, gprep, xp, xprep, ssa + (li + 1) * ssw_, T, slab,
+                split_ok,
+                li + 1 < L_ ? u16p(layers_[li + 1].attn_normprep) : nullptr);
             ck("w2", li);
         }
         return x;
@@ -581,8 +589,9 @@ class SliceEngine {
         if (out_mfma_) {
             (void)hipMemsetAsync(ss_tmp_.data_ptr(), 0, sizeof(float) * T, s);
             launch_prep_x(s, xin.data_ptr<float>(), u16p(xprep_),
-                          ss_tmp_.data_ptr<float>(), E_, T, jt_width(T));
-            launch_lmhead(s, mout_.w, u16p(xprep_), u16p(final_normprep_),
+                          ss_tmp_.data_ptr<float>(), E_, T, jt_width(T),
+                          u16p(final_normprep_));
+            launch_lmhead(s, mout_.w, u16p(xprep_),
                           ss_tmp_.data_ptr<float>(), eps_,
                           lg.data_ptr<float>(), T);
         } else {
@@ -726,9 +735,9 @@ class SliceEngine {
             reinterpret_cast<unsigned long long*>(score_key_.data_ptr());
         (void)hipMemsetAsync(ss, 0, sizeof(float) * ss_score_.numel(), s);
         launch_prep_x(s, x.data_ptr<float>(), u16p(xprep_), ss, E_, T,
-                      score_jt_width(T));
-        launch_lmhead_score(s, mout_.w, u16p(xprep_), u16p(final_normprep_),
-                            ss, eps_, targets.data_ptr<int>(), pkey,
+                      score_jt_width(T), u16p(final_normprep_));
+        launch_lmhead_score(s, mout_.w, u16p(xprep_), ss, eps_,
+                            targets.data_ptr<int>(), pkey,
                             score_sum_.data_ptr<float>(),
                             score_tgt_.data_ptr<float>(), T);
         launch_score_finish(s, pkey, score_sum_.data_ptr<float>(),
@@ -1198,9 +1207,11 @@ struct Panel {
     int jtw;
 };
 
-// x [T, cols] -> f16 panel + sumsq, then the dead columns filled
+// x [T, cols] -> f16 panel + sumsq, then the dead columns filled. normprep
+// is the padded norm plane of a NORM consumer (the prep step multiplies it
+// in), or undefined for a plain panel.
 Panel stage_panel(hipStream_t s, const torch::Tensor& x, int cols, int T,
-                  int16_t fill) {
+                  int16_t fill, torch::Tensor normprep = torch::Tensor()) {
     auto dev = torch::TensorOptions().device(torch::kCUDA);
     Panel p;
     p.jtw = jt_width(T);
@@ -1208,7 +1219,8 @@ Panel stage_panel(hipStream_t s, const torch::Tensor& x, int cols, int T,
     p.prep = torch::zeros({side_numel(cols, p.jtw)}, dev.dtype(torch::kInt16));
     p.ss = torch::zeros({sumsq_numel(T)}, dev.dtype(torch::kFloat32));
     launch_prep_x(s, x.data_ptr<float>(), u16p(p.prep),
-                  p.ss.data_ptr<float>(), cols, T, p.jtw);
+                  p.ss.data_ptr<float>(), cols, T, p.jtw,
+                  normprep.defined() ? u16p(normprep) : nullptr);
     if (T < p.jtw * 16)
         p.prep.narrow(0, 0, (int64_t)(cols / 8) * p.jtw * 128)
             .view({cols / 8, (int64_t)p.jtw * 16, 8})
@@ -1226,10 +1238,13 @@ torch::Tensor zero_side(int64_t cols, int64_t jtw) {
 // y = y_in + mat . b through launch_gemm16_residual, split passed as
 // split_ok. split = true is refused unless gemm16_res_route then takes the
 // slab route 0 (T <= 64 and rows/16 even), so split names the route.
+// out_norm_w (f32 [rows], optional) stands for the norm weights of the NORM
+// kernel that reads xprep_out: with it the channel holds f16(y) * f16(w),
+// without it f16(y).
 // -> (y [T, rows] f32, xprep_out i16 flat, ss_out f32 [T up to 64], jtw)
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, int64_t>
 gemm_residual(py::tuple mat, torch::Tensor b, torch::Tensor y_in, bool split,
-              int64_t dead_fill) {
+              int64_t dead_fill, py::object out_norm_w) {
     DevMat2 m = mat_arg(mat, "mat");
     const int T = check_panel_input(b, m.w.cols, "b");
     check_f32(y_in, "y_in");
@@ -1237,6 +1252,9 @@ gemm_residual(py::tuple mat, torch::Tensor b, torch::Tensor y_in, bool split,
                     y_in.size(1) == m.w.rows,
                 "y_in must be [T, rows]");
     const int16_t fill = check_dead_fill(dead_fill);
+    torch::Tensor out_plane;
+    if (!out_norm_w.is_none())
+        out_plane = check_norm_w(out_norm_w.cast<torch::Tensor>(), m.w.rows);
     TORCH_CHECK(!split || gemm16_res_route(m.w.rows, T, 1) == 0,
                 "split-K is a decode route (T <= 64), taken only when "
                 "rows/16 is even");
@@ -1254,8 +1272,28 @@ gemm_residual(py::tuple mat, torch::Tensor b, torch::Tensor y_in, bool split,
     launch_gemm16_residual(s, m.w, u16p(p.prep), y.data_ptr<float>(),
                            u16p(xo), sso.data_ptr<float>(), T,
                            split ? slab.data_ptr<float>() : nullptr,
-                           split ? 1 : 0);
+                           split ? 1 : 0,
+                           out_plane.defined() ? u16p(out_plane) : nullptr);
     return {y, xo, sso, (int64_t)p.jtw};
+}
+
+// The prep step alone: launch_prep_x of x [T, cols] at panel width
+// jt_width(T), with the padded plane of norm_w (f32 [cols]) or, for None,
+// no plane. -> (xprep i16 flat, ss f32 [T up to 64], jtw)
+std::tuple<torch::Tensor, torch::Tensor, int64_t> prep_panel(
+    torch::Tensor x, py::object norm_w) {
+    check_f32(x, "x");
+    TORCH_CHECK(x.dim() == 2 && x.size(1) >= 32 && x.size(1) % 32 == 0 &&
+                    x.size(1) <= ((int64_t)1 << 16),
+                "x must be [T, cols], cols a multiple of 32");
+    const int cols = (int)x.size(1);
+    const int T = check_panel_input(x, cols, "x");
+    torch::Tensor plane;
+    if (!norm_w.is_none())
+        plane = check_norm_w(norm_w.cast<torch::Tensor>(), cols);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    Panel p = stage_panel(s, x, cols, T, 0, plane);
+    return {p.prep, p.ss, (int64_t)p.jtw};
 }
 
 // logits [T, rows] = mat . rmsnorm(x) * norm_w: launch_prep_x +
@@ -1270,13 +1308,12 @@ torch::Tensor gemm_lmhead(py::tuple mat, torch::Tensor x,
     auto normprep = check_norm_w(norm_w, m.w.cols);
     const int16_t fill = check_dead_fill(dead_fill);
     hipStream_t s = c10::hip::getCurrentHIPStream().stream();
-    Panel p = stage_panel(s, x, m.w.cols, T, fill);
+    Panel p = stage_panel(s, x, m.w.cols, T, fill, normprep);
     auto lg = torch::zeros(
         {T, m.w.rows},
         torch::TensorOptions().device(torch::kCUDA).dtype(torch::kFloat32));
-    launch_lmhead(s, m.w, u16p(p.prep), u16p(normprep),
-                  p.ss.data_ptr<float>(), (float)eps, lg.data_ptr<float>(),
-                  T);
+    launch_lmhead(s, m.w, u16p(p.prep), p.ss.data_ptr<float>(), (float)eps,
+                  lg.data_ptr<float>(), T);
     return lg;
 }
 
@@ -1296,10 +1333,10 @@ std::tuple<torch::Tensor, int64_t> ffn_gate(py::tuple m1, py::tuple m3,
     auto normprep = check_norm_w(norm_w, a.w.cols);
     const int16_t fill = check_dead_fill(dead_fill);
     hipStream_t s = c10::hip::getCurrentHIPStream().stream();
-    Panel p = stage_panel(s, x, a.w.cols, T, fill);
+    Panel p = stage_panel(s, x, a.w.cols, T, fill, normprep);
     auto g = zero_side(a.w.rows, p.jtw);
-    launch_ffn16(s, a.w, c.w, u16p(p.prep), u16p(normprep),
-                 p.ss.data_ptr<float>(), (float)eps, u16p(g), T);
+    launch_ffn16(s, a.w, c.w, u16p(p.prep), p.ss.data_ptr<float>(),
+                 (float)eps, u16p(g), T);
     return {g, (int64_t)p.jtw};
 }
 
@@ -1347,12 +1384,12 @@ torch::Tensor qkv_project(py::tuple mq, py::tuple mk, py::tuple mv,
     auto f32 = torch::TensorOptions().device(torch::kCUDA).dtype(
         torch::kFloat32);
     hipStream_t s = c10::hip::getCurrentHIPStream().stream();
-    Panel p = stage_panel(s, x, E, T, fill);
+    Panel p = stage_panel(s, x, E, T, fill, normprep);
     auto qb = torch::zeros({T, E}, f32);
     TORCH_CHECK(qkv16_ks(E, d.Ekv) <= kMaxSplit, "split factor out of range");
     auto slab = torch::zeros({slab_numel((E + 2 * d.Ekv) / 16)}, f32);
-    launch_qkv16(s, q.w, k.w, v.w, u16p(p.prep), u16p(normprep),
-                 p.ss.data_ptr<float>(), (float)eps, qb.data_ptr<float>(),
+    launch_qkv16(s, q.w, k.w, v.w, u16p(p.prep), p.ss.data_ptr<float>(),
+                 (float)eps, qb.data_ptr<float>(),
                  h16(k_store), h16(v_store), pos.data_ptr<int>(),
                  seq.data_ptr<int>(), inv_freq.data_ptr<float>(), E, d.Ekv,
                  d.D, d.ctx, T, slab.data_ptr<float>(), /*skip_finish=*/0);
@@ -1364,7 +1401,10 @@ torch::Tensor qkv_project(py::tuple mq, py::tuple mk, py::tuple mv,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     // test hooks (see above), not serving API
     m.def("gemm_residual", &gemm_residual, py::arg("mat"), py::arg("b"),
-          py::arg("y_in"), py::arg("split"), py::arg("dead_fill"));
+          py::arg("y_in"), py::arg("split"), py::arg("dead_fill"),
+          py::arg("out_norm_w") = py::none());
+    m.def("prep_panel", &prep_panel, py::arg("x"),
+          py::arg("norm_w") = py::none());
     m.def("gemm_lmhead", &gemm_lmhead, py::arg("mat"), py::arg("x"),
           py::arg("norm_w"), py::arg("eps"), py::arg("dead_fill"));
     m.def("ffn_gate", &ffn_gate, py::arg("m1"), py::arg("m3"), py::arg("x"),

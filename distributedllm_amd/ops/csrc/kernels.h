@@ -70,9 +70,17 @@ int qkv16_mt_rt(int E, int Ekv, int T);
 int gemm16_ks(int rows);
 int qkv16_ks(int E, int Ekv);
 
+// RMSNorm over the side channels. The NORM kernels (qkv, ffn, lm_head,
+// scoring) read an xprep that already holds f16(x) * norm_w and apply only
+// the per-token 1/rms from ss_in. So every producer of an xprep takes
+// `normprep`, the padded f16 norm plane (pad_normprep) of the kernel that
+// will READ that xprep: launch_prep_x and launch_gemm16_residual below.
+// nullptr stores the plain f16(x). The sumsq is always of the f32 x.
+
 // x [T, cols] -> f16 xprep panel of width jtw + sumsq (ss zeroed upstream)
 void launch_prep_x(hipStream_t s, const float* x, unsigned short* xprep,
-                   float* ss, int cols, int T, int jtw);
+                   float* ss, int cols, int T, int jtw,
+                   const unsigned short* normprep);
 
 // T <= 64: slab != nullptr enables the RT=2 + split-K slab path for small
 // models; returns 1 when the slab path ran. skip_finish=1 leaves the slabs
@@ -80,29 +88,29 @@ void launch_prep_x(hipStream_t s, const float* x, unsigned short* xprep,
 // slab and skip_finish and returns 0.
 int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
                  const WMat2& wv, const unsigned short* xprep,
-                 const unsigned short* normprep, const float* ss_in,
-                 float eps, float* q_buf, __half* k_cache_layer,
+                 const float* ss_in, float eps, float* q_buf,
+                 __half* k_cache_layer,
                  __half* v_cache_layer, const int* pos, const int* seq,
                  const float* inv_freq, int E, int Ekv, int D, int n_ctx,
                  int T, float* slab, int skip_finish);
 
 void launch_ffn16(hipStream_t s, const WMat2& w1, const WMat2& w3,
-                  const unsigned short* xprep,
-                  const unsigned short* normprep, const float* ss_in,
+                  const unsigned short* xprep, const float* ss_in,
                   float eps, unsigned short* gprep, int T);
 
-// wo / w2: y += w . b, then sumsq of y into ss_out and f16(y) into
-// xprep_out. slab (rows/16 * gemm16_ks(rows) * 64 * 16 floats) is touched
-// by route 0 only; split_ok = 0 needs none.
+// wo / w2: y += w . b, then sumsq of y into ss_out and f16(y) (times
+// normprep, the next NORM kernel's plane, unless nullptr) into xprep_out.
+// slab (rows/16 * gemm16_ks(rows) * 64 * 16 floats) is touched by route 0
+// only; split_ok = 0 needs none.
 void launch_gemm16_residual(hipStream_t s, const WMat2& w,
                             const unsigned short* bprep, float* y,
                             unsigned short* xprep_out, float* ss_out, int T,
-                            float* slab, int split_ok);
+                            float* slab, int split_ok,
+                            const unsigned short* normprep);
 
 // lm_head, T <= 64: y = w . rmsnorm(b), plain f32 store
 void launch_lmhead(hipStream_t s, const WMat2& w,
-                   const unsigned short* bprep,
-                   const unsigned short* normprep, const float* ss_in,
+                   const unsigned short* bprep, const float* ss_in,
                    float eps, float* y, int T);
 
 void launch_rmsnorm(hipStream_t s, const float* x, const float* w, float* y,
@@ -273,8 +281,9 @@ void launch_logprobs(hipStream_t s, const float* logits, const int* rows,
 // [T, E] activation block, plus the row's arg-max, without ever forming
 // [T, V] logits. Three launches on one stream:
 //   launch_prep_x        at the scoring panel width score_jt_width(T)
-//                        (whole 4-tile groups at every T); ss zeroed
-//                        upstream, ss must hold T rounded up to 64 floats
+//                        (whole 4-tile groups at every T) with the final
+//                        norm plane; ss zeroed upstream, ss must hold T
+//                        rounded up to 64 floats
 //   launch_lmhead_score k_lmhead_score: fused final norm + lm_head with a
 //                        log-sum-exp epilogue -> P = V / (16 * RT) partials
 //                        per token, pkey/psum [T][P], and tgt_logit [T]
@@ -285,8 +294,7 @@ int lmhead_score_rt(int V, int T);
 int score_jt_width(int T);
 
 void launch_lmhead_score(hipStream_t s, const WMat2& w,
-                         const unsigned short* bprep,
-                         const unsigned short* normprep, const float* ss_in,
+                         const unsigned short* bprep, const float* ss_in,
                          float eps, const int* targets,
                          unsigned long long* pkey, float* psum,
                          float* tgt_logit, int T);

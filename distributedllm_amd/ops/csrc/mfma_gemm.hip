@@ -21,8 +21,11 @@
 // Activations ride an f16 side channel ("xprep", layout
 // [cols/8][jtw][16][8] = exactly the B-fragment gather, see xprep_index)
 // written by the producing kernel's epilogue; the f32 residual stream
-// stays f32. RMSNorm is fused into the consumers' B-fragment build via a
-// sumsq side channel written by the previous residual epilogue.
+// stays f32. RMSNorm is split between the two sides of that channel: the
+// producer of an xprep that feeds a NORM consumer stores f16(x) * norm_w
+// (elementwise, once per element), and the consumers' B-fragment build
+// applies the per-token 1/rms from a sumsq side channel, which the
+// producers accumulate in f32 from the un-normalised x.
 //
 // A decode layer is 7-9 launches depending on model size: qkv (fused, or
 // RT=2 slab split-K whose finish is either k_qkv_finish or the attention
@@ -185,12 +188,18 @@ __device__ __forceinline__ void a_frag_q8(uint32_t qA, uint32_t qB,
 // xprep side channel (layout [kc][jtw][16][8]). Decode callers pass
 // (JT, 0); the large-M kernels tile a T-wide panel with jtw = ceil(T/16)
 // padded to the 4-tile group and jt0 = mtile*JT.
+// NORM: the panel holds v = f16(x) * norm_w, multiplied in by its producer
+// (k_prep_x, k_reduce_prep, the residual epilogues); the B fragment is
+// hmul2(v, scale) with scale = f16(rsqrt(ss_in / cols + eps)) per token
+// column. The norm weight never enters the K loop: no load, no register
+// and no multiply for it per K block. Two separate f16 multiplies do not
+// contract, so the fragment has the bits of (f16(x) * norm_w) * scale
+// computed in one place.
 template <int WT, bool NORM, int NM, int JT, int RT = 1, int PF = 4,
           int NW = NWAVES>
 __device__ __forceinline__ void wave_tile_kloop(
     const WMat2* const* ws, int tile_row,
     const unsigned short* __restrict__ xprep,
-    const unsigned short* __restrict__ normprep,
     const float* __restrict__ ss_in, float eps,
     float acc[RT][NM][JT][4], int b0, int b1, int jtw = JT, int jt0 = 0) {
     KLoop kl;
@@ -252,8 +261,6 @@ __device__ __forceinline__ void wave_tile_kloop(
     // xprep layout: element (kc, jt, j, e) at ((kc*jtw + jt)*16 + j)*8 + e
     const unsigned short* xp =
         xprep + ((size_t)(kl.kb0 * 4 + kl.ks) * jtw + jt0) * 128 + kl.i * 8;
-    const unsigned short* np =
-        normprep + (NORM ? (size_t)(kl.kb0 * 4 + kl.ks) * 8 : 0);
 
     struct Batch {  // weight stream only (HBM, nt, double-buffered)
         u32x4 q[(PF / 4) * QW][RT][NM], ab[PF / 4][RT][NM];
@@ -264,7 +271,6 @@ __device__ __forceinline__ void wave_tile_kloop(
     Batch bufA, bufB;
     struct XPanel {  // B-panel side channel (L2-resident, per iteration)
         uint4 xb[PF][JT];
-        uint4 nbv[PF];
     };
 
     auto load_w = [&](Batch& bt) {
@@ -313,29 +319,24 @@ __device__ __forceinline__ void wave_tile_kloop(
             for (int jt = 0; jt < JT; ++jt)
                 px.xb[u][jt] = *reinterpret_cast<const uint4*>(
                     xp + ((size_t)u * 4 * jtw + jt) * 128);  // 4 kc per kb
-            if (NORM)
-                px.nbv[u] = *reinterpret_cast<const uint4*>(np + u * 32);
         }
         xp += (size_t)PF * 4 * jtw * 128;
-        if (NORM) np += PF * 32;
     };
 
     auto compute_one = [&](int parity, const uint32_t q[RT][NM][QW],
                            const uint32_t ab[RT][NM],
-                           const uint4 aw[RT][NM], const uint4 xb[JT],
-                           const uint4& nbv) {
+                           const uint4 aw[RT][NM], const uint4 xb[JT]) {
         ABFrag b[JT];
 #pragma unroll
         for (int jt = 0; jt < JT; ++jt) {
             if (NORM) {
+                // the panel already holds f16(x) * norm_w (the producer's
+                // multiply); only the per-token factor is applied here
                 const uint32_t xw[4] = {xb[jt].x, xb[jt].y, xb[jt].z,
                                         xb[jt].w};
-                const uint32_t nw[4] = {nbv.x, nbv.y, nbv.z, nbv.w};
 #pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const __half2 v = __hmul2(u2h2(xw[w]), u2h2(nw[w]));
-                    b[jt].u[w] = h22u(__hmul2(v, scale2[jt]));
-                }
+                for (int w = 0; w < 4; ++w)
+                    b[jt].u[w] = h22u(__hmul2(u2h2(xw[w]), scale2[jt]));
             } else {
                 b[jt].u[0] = xb[jt].x;
                 b[jt].u[1] = xb[jt].y;
@@ -385,7 +386,7 @@ __device__ __forceinline__ void wave_tile_kloop(
                     }
                     ab[rt][n] = bt.ab[u / 4][rt][n][u % 4];
                 }
-            compute_one(u & 1, q, ab, bt.aw[u], px.xb[u], px.nbv[u]);
+            compute_one(u & 1, q, ab, bt.aw[u], px.xb[u]);
         }
     };
 
@@ -430,15 +431,11 @@ __device__ __forceinline__ void wave_tile_kloop(
     for (int g = kl.kb0 + nfull * PF; g < kl.kb1; ++g) {
         uint32_t q[RT][NM][QW], ab[RT][NM];
         uint4 aw[RT][NM];
-        uint4 xb[JT], nbv;
+        uint4 xb[JT];
 #pragma unroll
         for (int jt = 0; jt < JT; ++jt)
             xb[jt] = *reinterpret_cast<const uint4*>(xp + jt * 128);
         xp += (size_t)4 * jtw * 128;
-        if (NORM) {
-            nbv = *reinterpret_cast<const uint4*>(np);
-            np += 32;
-        }
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
@@ -456,7 +453,7 @@ __device__ __forceinline__ void wave_tile_kloop(
                     abp[rt][n] += 16;
                 }
             }
-        compute_one(g & 1, q, ab, aw, xb, nbv);
+        compute_one(g & 1, q, ab, aw, xb);
     }
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
@@ -525,6 +522,62 @@ __device__ __forceinline__ void slab_tile_store(float* dst,
     store_f4_wt(dst, make_float4(v[0], v[1], v[2], v[3]));
 }
 
+// ------------------------------------------------- norm-weight fold
+// The producer half of the fused RMSNorm: an xprep that feeds a NORM
+// consumer stores f16(x) * norm_w. normprep is the CONSUMER's padded f16
+// norm plane (pad_normprep), element e of the consumer's K axis at
+// normprep[e]; nullptr stores the plain f16(x) (non-NORM consumers, and an
+// xprep nobody reads). The sum of squares next to it is always taken from
+// the un-normalised f32 x.
+
+// 8 consecutive elements e = kc*8 .. kc*8+7, packed as the side channel
+// stores them
+__device__ __forceinline__ uint4 norm_fold8(
+    uint4 o, const unsigned short* __restrict__ normprep, int kc) {
+    if (normprep == nullptr) return o;
+    const uint4 n = *reinterpret_cast<const uint4*>(normprep + (size_t)kc * 8);
+    o.x = h22u(__hmul2(u2h2(o.x), u2h2(n.x)));
+    o.y = h22u(__hmul2(u2h2(o.y), u2h2(n.y)));
+    o.z = h22u(__hmul2(u2h2(o.z), u2h2(n.z)));
+    o.w = h22u(__hmul2(u2h2(o.w), u2h2(n.w)));
+    return o;
+}
+
+// 4 consecutive elements e = r0 .. r0+3 (r0 % 4 == 0): the 8 B chunk a
+// tile epilogue stores
+__device__ __forceinline__ uint2 norm_fold4(
+    uint2 o, const unsigned short* __restrict__ normprep, int r0) {
+    if (normprep == nullptr) return o;
+    const uint2 n = *reinterpret_cast<const uint2*>(normprep + r0);
+    o.x = h22u(__hmul2(u2h2(o.x), u2h2(n.x)));
+    o.y = h22u(__hmul2(u2h2(o.y), u2h2(n.y)));
+    return o;
+}
+
+// --------------------------------------------- sum of squares, pinned
+// The sumsq side channel ends in an f16 scale (wave_tile_kloop), so one
+// f32 ulp here can flip that rounding and move every output of a token.
+// Left to -ffp-contract=fast the compiler picks which products fuse into
+// FMAs from the code AROUND the sum, so an unrelated edit of a prep kernel
+// changed the engine's outputs. The two orders below are the ones each
+// kernel has always evaluated, written out so that they stay put:
+// k_prep_x adds unfused squares left to right, k_reduce_prep runs one FMA
+// chain per float4 that starts from y*y.
+__device__ __forceinline__ float sumsq8_unfused(float sum, const float4& a,
+                                                const float4& b) {
+#pragma clang fp contract(off)
+    sum += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
+    sum += b.x * b.x + b.y * b.y + b.z * b.z + b.w * b.w;
+    return sum;
+}
+
+__device__ __forceinline__ float sumsq4_fma(const float4& a) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(
+        a.w, a.w,
+        __builtin_fmaf(a.z, a.z, __builtin_fmaf(a.x, a.x, a.y * a.y)));
+}
+
 // ------------------------------------------------------------- k_prep_x
 // sumsq + f16 xprep of an incoming f32 activation block (forward entry,
 // split-K gemm epilogue, logits entry). Grid: (T, C) — C column chunks per
@@ -533,6 +586,7 @@ __device__ __forceinline__ void slab_tile_store(float* dst,
 // measured 4.6 µs — launch+latency bound on 16 CUs of 256).
 __global__ void k_prep_x(const float* __restrict__ x,
                          unsigned short* __restrict__ xprep,
+                         const unsigned short* __restrict__ normprep,
                          float* __restrict__ ss, int cols, int jtw) {
     const int t = blockIdx.x;
     const float* xt = x + (size_t)t * cols;
@@ -545,13 +599,13 @@ __global__ void k_prep_x(const float* __restrict__ x,
     for (int kc = kc0 + threadIdx.x; kc < kc1; kc += BLOCK) {
         const float4 a = *reinterpret_cast<const float4*>(xt + kc * 8);
         const float4 b = *reinterpret_cast<const float4*>(xt + kc * 8 + 4);
-        sum += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
-        sum += b.x * b.x + b.y * b.y + b.z * b.z + b.w * b.w;
+        sum = sumsq8_unfused(sum, a, b);
         uint4 o;
         o.x = pack_f16(a.x, a.y);
         o.y = pack_f16(a.z, a.w);
         o.z = pack_f16(b.x, b.y);
         o.w = pack_f16(b.z, b.w);
+        o = norm_fold8(o, normprep, kc);
         // xprep_index(kc * 8, t, jtw), spelled out (see the epilogue note)
         *reinterpret_cast<uint4*>(
             xprep + (((size_t)kc * jtw + (t >> 4)) * 16 + (t & 15)) * 8) = o;
@@ -569,9 +623,11 @@ __global__ void k_prep_x(const float* __restrict__ x,
 // slab partials, then sumsq + f16 xprep of the result (replaces atomic
 // split-K partials + a separate k_prep_x — the 819K atomicAdd/kernel of
 // the atomic form dominated at JT=4). Grid (T, C); ss zeroed upstream.
+// normprep: the norm plane of the xprep's consumer, or nullptr.
 __global__ void k_reduce_prep(float* __restrict__ y,
                               const float* __restrict__ slab, int ks,
                               unsigned short* __restrict__ xprep,
+                              const unsigned short* __restrict__ normprep,
                               float* __restrict__ ss, int cols, int jtw) {
     const int t = blockIdx.x;
     float* yt = y + (size_t)t * cols;
@@ -600,13 +656,14 @@ __global__ void k_reduce_prep(float* __restrict__ y,
         }
         *reinterpret_cast<float4*>(yt + kc * 8) = a;
         *reinterpret_cast<float4*>(yt + kc * 8 + 4) = b;
-        sum += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
-        sum += b.x * b.x + b.y * b.y + b.z * b.z + b.w * b.w;
+        sum += sumsq4_fma(a);
+        sum += sumsq4_fma(b);
         uint4 o;
         o.x = pack_f16(a.x, a.y);
         o.y = pack_f16(a.z, a.w);
         o.z = pack_f16(b.x, b.y);
         o.w = pack_f16(b.z, b.w);
+        o = norm_fold8(o, normprep, kc);
         *reinterpret_cast<uint4*>(xprep + xprep_index(kc * 8, t, jtw)) = o;
     }
     sum = wave_reduce_sum(sum);
@@ -627,6 +684,8 @@ __global__ void k_reduce_prep(float* __restrict__ y,
 //   GM_RES_SQ     unsplit wo / w2 with the fused residual + sumsq + xprep
 //                 epilogue (taken when E/16 is odd, or by DLLM_NO_SPLITK).
 //   GM_NORM_PLAIN lm_head: input RMSNorm fused, plain f32 store.
+// normprep is the norm plane of xprep_out's consumer (GM_RES_SQ, may be
+// nullptr); the other modes write no xprep and ignore it.
 template <int WT, int MODE, int JT, int RT = 1>
 __global__ __launch_bounds__(BLOCK) void k_gemm16(
     WMat2 w, const unsigned short* __restrict__ bprep,
@@ -649,8 +708,8 @@ __global__ __launch_bounds__(BLOCK) void k_gemm16(
         b0 = min(nbk, (int)blockIdx.y * per);
         b1 = min(nbk, b0 + per);
     }
-    wave_tile_kloop<WT, NORM, 1, JT, RT>(ws, blockIdx.x, bprep, normprep,
-                                         ss_in, eps, acc, b0, b1);
+    wave_tile_kloop<WT, NORM, 1, JT, RT>(ws, blockIdx.x, bprep, ss_in, eps,
+                                         acc, b0, b1);
     __shared__ float lds[3 * 64 * 4 * JT * RT];
     combine_acc<RT * JT>(reinterpret_cast<float(*)[4]>(acc), lds);
     if (threadIdx.x >= WAVE) return;
@@ -702,6 +761,7 @@ __global__ __launch_bounds__(BLOCK) void k_gemm16(
             uint2 o;
             o.x = pack_f16(acc[rt][0][jt][0], acc[rt][0][jt][1]);
             o.y = pack_f16(acc[rt][0][jt][2], acc[rt][0][jt][3]);
+            o = norm_fold4(o, normprep, r0);
             *reinterpret_cast<uint2*>(
                 xprep_out + (((size_t)(r0 >> 3) * JT + jt) * 16 + j) * 8 +
                 (r0 & 7)) = o;
@@ -729,7 +789,6 @@ __global__ __launch_bounds__(BLOCK) void k_gemm16(
 template <int WT, int JT, int RT>
 __global__ __launch_bounds__(BLOCK) void k_qkv16_slab(
     WMat2 wq, WMat2 wk, WMat2 wv, const unsigned short* __restrict__ xprep,
-    const unsigned short* __restrict__ normprep,
     const float* __restrict__ ss_in, float eps, float* __restrict__ slab,
     int E, int Ekv, int T) {
     const int tq = (E >> 4) / RT;
@@ -748,8 +807,8 @@ __global__ __launch_bounds__(BLOCK) void k_qkv16_slab(
     per = (per + 3) & ~3;
     const int b0 = min(nbe, (int)blockIdx.y * per);
     const int b1 = min(nbe, b0 + per);
-    wave_tile_kloop<WT, true, 1, JT, RT>(ws, stile, xprep, normprep, ss_in,
-                                         eps, acc, b0, b1);
+    wave_tile_kloop<WT, true, 1, JT, RT>(ws, stile, xprep, ss_in, eps, acc,
+                                         b0, b1);
     __shared__ float lds[3 * 64 * 4 * RT * JT];
     combine_acc<RT * JT>(reinterpret_cast<float(*)[4]>(acc), lds);
     if (threadIdx.x >= WAVE) return;
@@ -881,7 +940,6 @@ static inline int xcd_grid(int GT, int MT) {
 template <int WT, int JT, int RT = 1, bool MTK = false>
 __global__ __launch_bounds__(BLOCK) void k_qkv16(
     WMat2 wq, WMat2 wk, WMat2 wv, const unsigned short* __restrict__ xprep,
-    const unsigned short* __restrict__ normprep,
     const float* __restrict__ ss_in, float eps, float* __restrict__ q_buf,
     __half* __restrict__ k_cache, __half* __restrict__ v_cache,
     const int* __restrict__ pos, const int* __restrict__ seq,
@@ -911,9 +969,8 @@ __global__ __launch_bounds__(BLOCK) void k_qkv16(
     float acc[RT][1][JT][4];
     const WMat2* ws[1] = {&w};
     const int nbe = (WT == W_F16) ? (E >> 5) : (((E >> 5) + 3) & ~3);
-    wave_tile_kloop<WT, true, 1, JT, RT>(ws, tile, xprep, normprep, ss_in,
-                                         eps, acc, 0, nbe, jtw,
-                                         mtile * JT);
+    wave_tile_kloop<WT, true, 1, JT, RT>(ws, tile, xprep, ss_in, eps, acc,
+                                         0, nbe, jtw, mtile * JT);
     __shared__ float lds[3 * 64 * 4 * JT * RT];
     combine_acc<RT * JT>(reinterpret_cast<float(*)[4]>(acc), lds);
     if (threadIdx.x >= WAVE) return;
@@ -967,6 +1024,7 @@ template <int WT, int JT = 4, int RT = 1>
 __global__ __launch_bounds__(BLOCK) void k_gemm16_mt(
     WMat2 w, const unsigned short* __restrict__ bprep,
     float* __restrict__ y, unsigned short* __restrict__ xprep_out,
+    const unsigned short* __restrict__ normprep,
     float* __restrict__ ss_out, int T, int MT, int jtw) {
     int gtile, mtile;
     const int GT = (w.rows >> 4) / RT;
@@ -978,9 +1036,8 @@ __global__ __launch_bounds__(BLOCK) void k_gemm16_mt(
     const WMat2* ws[1] = {&w};
     const int nbt = w.cols >> 5;
     const int nbk = (WT == W_F16) ? nbt : ((nbt + 3) & ~3);
-    wave_tile_kloop<WT, false, 1, JT, RT>(ws, gtile, bprep, nullptr,
-                                          nullptr, 0.f, acc, 0, nbk, jtw,
-                                          mtile * JT);
+    wave_tile_kloop<WT, false, 1, JT, RT>(ws, gtile, bprep, nullptr, 0.f,
+                                          acc, 0, nbk, jtw, mtile * JT);
     __shared__ float lds[3 * 64 * 4 * JT * RT];
     combine_acc<RT * JT>(reinterpret_cast<float(*)[4]>(acc), lds);
     if (threadIdx.x >= WAVE) return;
@@ -1004,6 +1061,7 @@ __global__ __launch_bounds__(BLOCK) void k_gemm16_mt(
             uint2 o;
             o.x = pack_f16(acc[rt][0][jt][0], acc[rt][0][jt][1]);
             o.y = pack_f16(acc[rt][0][jt][2], acc[rt][0][jt][3]);
+            o = norm_fold4(o, normprep, r0);
             *reinterpret_cast<uint2*>(
                 xprep_out +
                 (((size_t)(r0 >> 3) * jtw + mtile * JT + jt) * 16 + j) * 8 +
@@ -1024,7 +1082,6 @@ __global__ __launch_bounds__(BLOCK) void k_gemm16_mt(
 template <int WT, int JT, int RT = 1, bool MTK = false>
 __global__ __launch_bounds__(BLOCK) void k_ffn16(
     WMat2 w1, WMat2 w3, const unsigned short* __restrict__ xprep,
-    const unsigned short* __restrict__ normprep,
     const float* __restrict__ ss_in, float eps,
     unsigned short* __restrict__ gprep, int T, int MT, int jtw_rt) {
     int gtile, mtile, jtw;
@@ -1044,9 +1101,8 @@ __global__ __launch_bounds__(BLOCK) void k_ffn16(
     const WMat2* ws[2] = {&w1, &w3};
     const int nbf = (WT == W_F16) ? (w1.cols >> 5)
                                   : (((w1.cols >> 5) + 3) & ~3);
-    wave_tile_kloop<WT, true, 2, JT, RT>(ws, gtile, xprep, normprep, ss_in,
-                                         eps, acc, 0, nbf, jtw,
-                                         mtile * JT);
+    wave_tile_kloop<WT, true, 2, JT, RT>(ws, gtile, xprep, ss_in, eps, acc,
+                                         0, nbf, jtw, mtile * JT);
     __shared__ float lds[3 * 64 * 4 * 2 * JT * RT];
     combine_acc<RT * 2 * JT>(reinterpret_cast<float(*)[4]>(acc), lds);
     if (threadIdx.x >= WAVE) return;
@@ -1089,7 +1145,6 @@ __global__ __launch_bounds__(BLOCK) void k_ffn16(
 template <int WT, int RT>
 __global__ __launch_bounds__(BLOCK) void k_lmhead_score(
     WMat2 w, const unsigned short* __restrict__ bprep,
-    const unsigned short* __restrict__ normprep,
     const float* __restrict__ ss_in, float eps,
     const int* __restrict__ targets, unsigned long long* __restrict__ pkey,
     float* __restrict__ psum, float* __restrict__ tgt_logit, int T, int MT,
@@ -1105,8 +1160,8 @@ __global__ __launch_bounds__(BLOCK) void k_lmhead_score(
     const WMat2* ws[1] = {&w};
     const int nbt = w.cols >> 5;
     const int nbk = (WT == W_F16) ? nbt : ((nbt + 3) & ~3);
-    wave_tile_kloop<WT, true, 1, JT, RT>(ws, gtile, bprep, normprep, ss_in,
-                                         eps, acc, 0, nbk, jtw, mtile * JT);
+    wave_tile_kloop<WT, true, 1, JT, RT>(ws, gtile, bprep, ss_in, eps, acc,
+                                         0, nbk, jtw, mtile * JT);
     __shared__ float lds[3 * 64 * 4 * JT * RT];
     combine_acc<RT * JT>(reinterpret_cast<float(*)[4]>(acc), lds);
     if (threadIdx.x >= WAVE) return;
@@ -1187,11 +1242,13 @@ static inline dim3 prep_grid(int cols, int T) {
 }
 
 // jtw: jt_width(T) for the layer path and the lm_head, score_jt_width(T)
-// for prompt scoring; ss zeroed upstream
+// for prompt scoring; ss zeroed upstream. normprep: the norm plane of the
+// NORM kernel that will read xprep (nullptr = plain f16(x))
 void launch_prep_x(hipStream_t s, const float* x, unsigned short* xprep,
-                   float* ss, int cols, int T, int jtw) {
+                   float* ss, int cols, int T, int jtw,
+                   const unsigned short* normprep) {
     hipLaunchKernelGGL(k_prep_x, prep_grid(cols, T), dim3(BLOCK), 0, s, x,
-                       xprep, ss, cols, jtw);
+                       xprep, normprep, ss, cols, jtw);
 }
 
 #define DISPATCH_JT(JTV, ...)            \
@@ -1356,8 +1413,8 @@ int qkv16_mt_rt(int E, int Ekv, int T) {
 
 int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
                  const WMat2& wv, const unsigned short* xprep,
-                 const unsigned short* normprep, const float* ss_in,
-                 float eps, float* q_buf, __half* k_cache_layer,
+                 const float* ss_in, float eps, float* q_buf,
+                 __half* k_cache_layer,
                  __half* v_cache_layer, const int* pos, const int* seq,
                  const float* inv_freq, int E, int Ekv, int D, int n_ctx,
                  int T, float* slab, int skip_finish) {
@@ -1369,7 +1426,7 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
             hipLaunchKernelGGL(
                 (k_qkv16<WTc, 4, RTc, true>),
                 dim3(xcd_grid(tiles3 / RTc, MT)), dim3(BLOCK), 0, s, wq, wk,
-                wv, xprep, normprep, ss_in, eps, q_buf, k_cache_layer,
+                wv, xprep, ss_in, eps, q_buf, k_cache_layer,
                 v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T, MT,
                 jtw)));
         return 0;
@@ -1381,7 +1438,7 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
         const dim3 grid(tiles3 / 2, ks);
         DISPATCH_WT2(wq.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
             (k_qkv16_slab<WTc, JTc, 2>), grid, dim3(BLOCK), 0, s, wq, wk,
-            wv, xprep, normprep, ss_in, eps, slab, E, Ekv, T)));
+            wv, xprep, ss_in, eps, slab, E, Ekv, T)));
         if (!skip_finish) {
             const int total = ((E + 2 * Ekv) / 8) * T;
             hipLaunchKernelGGL(k_qkv_finish,
@@ -1396,7 +1453,7 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
     DISPATCH_RT2(route, DISPATCH_WT2(wq.wtype, DISPATCH_JT(pick_jt(T),
         hipLaunchKernelGGL(
             (k_qkv16<WTc, JTc, RTc>), dim3(tiles3 / RTc), dim3(BLOCK), 0, s,
-            wq, wk, wv, xprep, normprep, ss_in, eps, q_buf, k_cache_layer,
+            wq, wk, wv, xprep, ss_in, eps, q_buf, k_cache_layer,
             v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T, 0, 0))));
     return 0;
 }
@@ -1404,8 +1461,7 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
 // ffn stays fused at every T: a slab+finish variant measured slower at
 // every split/occupancy combination tried and was removed
 void launch_ffn16(hipStream_t s, const WMat2& w1, const WMat2& w3,
-                  const unsigned short* xprep,
-                  const unsigned short* normprep, const float* ss_in,
+                  const unsigned short* xprep, const float* ss_in,
                   float eps, unsigned short* gprep, int T) {
     const int tilesF = w1.rows / 16;
     const int rt = ffn16_rt(w1.rows, T);
@@ -1414,20 +1470,21 @@ void launch_ffn16(hipStream_t s, const WMat2& w1, const WMat2& w3,
         const int jtw = jt_width(T);
         DISPATCH_RT2(rt, DISPATCH_WT2(w1.wtype, hipLaunchKernelGGL(
             (k_ffn16<WTc, 4, RTc, true>), dim3(xcd_grid(tilesF / RTc, MT)),
-            dim3(BLOCK), 0, s, w1, w3, xprep, normprep, ss_in, eps, gprep, T,
-            MT, jtw)));
+            dim3(BLOCK), 0, s, w1, w3, xprep, ss_in, eps, gprep, T, MT,
+            jtw)));
         return;
     }
     DISPATCH_RT2(rt, DISPATCH_WT2(w1.wtype, DISPATCH_JT(pick_jt(T),
         hipLaunchKernelGGL(
             (k_ffn16<WTc, JTc, RTc>), dim3(tilesF / RTc), dim3(BLOCK), 0, s,
-            w1, w3, xprep, normprep, ss_in, eps, gprep, T, 0, 0))));
+            w1, w3, xprep, ss_in, eps, gprep, T, 0, 0))));
 }
 
 void launch_gemm16_residual(hipStream_t s, const WMat2& w,
                             const unsigned short* bprep, float* y,
                             unsigned short* xprep_out, float* ss_out, int T,
-                            float* slab, int split_ok) {
+                            float* slab, int split_ok,
+                            const unsigned short* normprep) {
     const int R = w.rows / 16;
     switch (gemm16_res_route(w.rows, T, split_ok)) {
         case 0: {
@@ -1441,13 +1498,13 @@ void launch_gemm16_residual(hipStream_t s, const WMat2& w,
             // y[t] += sum of the ks partials, then sumsq + xprep of y
             hipLaunchKernelGGL(k_reduce_prep, prep_grid(w.rows, T),
                                dim3(BLOCK), 0, s, y, slab, ks, xprep_out,
-                               ss_out, w.rows, pick_jt(T));
+                               normprep, ss_out, w.rows, pick_jt(T));
             break;
         }
         case 1:
             DISPATCH_WT2(w.wtype, DISPATCH_JT(pick_jt(T), hipLaunchKernelGGL(
                 (k_gemm16<WTc, GM_RES_SQ, JTc, 1>), dim3(R), dim3(BLOCK), 0,
-                s, w, bprep, nullptr, nullptr, 0.f, y, xprep_out, ss_out,
+                s, w, bprep, normprep, nullptr, 0.f, y, xprep_out, ss_out,
                 T)));
             break;
         default: {
@@ -1456,22 +1513,21 @@ void launch_gemm16_residual(hipStream_t s, const WMat2& w,
             DISPATCH_RT2(gemm16_mt_rt(w.rows, T), DISPATCH_WT2(w.wtype,
                 hipLaunchKernelGGL(
                     (k_gemm16_mt<WTc, 4, RTc>), dim3(xcd_grid(R / RTc, MT)),
-                    dim3(BLOCK), 0, s, w, bprep, y, xprep_out, ss_out, T, MT,
-                    jtw)));
+                    dim3(BLOCK), 0, s, w, bprep, y, xprep_out, normprep,
+                    ss_out, T, MT, jtw)));
         }
     }
 }
 
 void launch_lmhead(hipStream_t s, const WMat2& w,
-                   const unsigned short* bprep,
-                   const unsigned short* normprep, const float* ss_in,
+                   const unsigned short* bprep, const float* ss_in,
                    float eps, float* y, int T) {
     const int R = w.rows / 16;
     const int rt = gemm16_plain_rt(w.rows);
     DISPATCH_RT4(rt, DISPATCH_WT2(w.wtype, DISPATCH_JT(pick_jt(T),
         hipLaunchKernelGGL(
             (k_gemm16<WTc, GM_NORM_PLAIN, JTc, RTc>), dim3(R / RTc),
-            dim3(BLOCK), 0, s, w, bprep, normprep, ss_in, eps, y, nullptr,
+            dim3(BLOCK), 0, s, w, bprep, nullptr, ss_in, eps, y, nullptr,
             nullptr, T))));
 }
 
@@ -1494,8 +1550,7 @@ int lmhead_score_rt(int V, int T) {
 }
 
 void launch_lmhead_score(hipStream_t s, const WMat2& w,
-                         const unsigned short* bprep,
-                         const unsigned short* normprep, const float* ss_in,
+                         const unsigned short* bprep, const float* ss_in,
                          float eps, const int* targets,
                          unsigned long long* pkey, float* psum,
                          float* tgt_logit, int T) {
@@ -1505,6 +1560,6 @@ void launch_lmhead_score(hipStream_t s, const WMat2& w,
     const int rt = lmhead_score_rt(w.rows, T);
     DISPATCH_RT4(rt, DISPATCH_WT2(w.wtype, hipLaunchKernelGGL(
         (k_lmhead_score<WTc, RTc>), dim3(xcd_grid(R / RTc, MT)), dim3(BLOCK),
-        0, s, w, bprep, normprep, ss_in, eps, targets, pkey, psum, tgt_logit,
-        T, MT, jtw)));
+        0, s, w, bprep, ss_in, eps, targets, pkey, psum, tgt_logit, T, MT,
+        jtw)));
 }
