@@ -356,7 +356,8 @@ class BatchGenerateCommand(Command):
         # the shared prefix lives in one KV slot of its own
         extra = 1 if args.shared_prefix_file else 0
         eng = engine_for_slice(f, n_ctx=args.ctx, max_batch=n_slots + extra,
-                               kv_dtype=args.kv_dtype)
+                               kv_dtype=args.kv_dtype,
+                               kv8_prefix=_wants_kv8_prefix(args))
         eng.attach_extra(slicer.make_extra_layers(f))
         tok = Tokenizer(f.vocab)
         prefix = _read_shared_prefix(args.shared_prefix_file, tok)
@@ -417,7 +418,14 @@ _SHARED_PREFIX_HELP = (
 _KV_DTYPE_HELP = (
     "KV cache element type: q8 stores int8 rows with one f16 scale per "
     "(row, KV head): half the KV bytes of f16 (twice the slots or context "
-    "for the same HBM); not combinable with --shared-prefix-file")
+    "for the same HBM); with --shared-prefix-file the prefix slot is read "
+    "as bytes too")
+
+
+def _wants_kv8_prefix(args) -> bool:
+    """q8 engines serve a shared prefix only when built with kv8_prefix:
+    both options together switch it on."""
+    return args.kv_dtype == "q8" and bool(args.shared_prefix_file)
 
 
 def _read_shared_prefix(path, tok):
@@ -505,7 +513,8 @@ class ServeHttpCommand(Command):
                 fit = max(1, int((260e9 - w_bytes) // max(kv, 1)))
                 n_lanes = min(5, fit) if fit >= 3 else 1
         eng = engine_for_slice(f, n_ctx=args.ctx, max_batch=args.slots,
-                               kv_dtype=args.kv_dtype)
+                               kv_dtype=args.kv_dtype,
+                               kv8_prefix=_wants_kv8_prefix(args))
         eng.attach_extra(slicer.make_extra_layers(f))
         lanes = None
         if n_lanes > 1 and hasattr(eng, "clone_shared"):

@@ -59,7 +59,7 @@ class HIPSliceEngine:
                  n_ctx: int = 2048, max_batch: int = 16,
                  max_prefill: Optional[int] = None,
                  gqa_attention: bool = True, kv_dtype: str = "f16",
-                 kv8_prefill: bool = True):
+                 kv8_prefill: bool = True, kv8_prefix: bool = False):
         from .. import ops
         core = ops.core()
         self.hp = hp
@@ -71,11 +71,15 @@ class HIPSliceEngine:
         # the (token, KV head) matrix-core kernel; False keeps k_attention
         self.gqa_attention = gqa_attention
         # "q8": int8 KV cache with one f16 scale per (row, KV head): half
-        # the KV bytes, attention on k_attn_kv8; no prefix=
+        # the KV bytes, attention on k_attn_kv8; prefix= only with
+        # kv8_prefix
         self.kv_dtype = _check_kv_dtype(kv_dtype)
         # q8 prompt spans of more than 64 tokens in one call: the Q-tiled
         # k_attn_kv8_prefill; False keeps k_attn_kv8 at every T
         self.kv8_prefill = kv8_prefill
+        # q8 serves prefix= on k_attn_kv8_prefix + k_attn_kv8_prefix_tail;
+        # False keeps the refusal
+        self.kv8_prefix = kv8_prefix
         # prefill token cap per forward call (side channels scale with it;
         # larger prompts tile host-side in max_prefill chunks)
         if max_prefill is None:
@@ -86,7 +90,8 @@ class HIPSliceEngine:
             eps=RMS_EPS, rope_base=ROPE_BASE, max_prefill=max_prefill,
             n_head_kv=hp.kv_heads if hp.is_gqa else 0,
             gqa_attention=gqa_attention,
-            kv_dtype=KV_DTYPES.index(kv_dtype), kv8_prefill=kv8_prefill)
+            kv_dtype=KV_DTYPES.index(kv_dtype), kv8_prefill=kv8_prefill,
+            kv8_prefix=kv8_prefix)
         self.device = "cuda"
         self.has_extra = False
         # weight-tensor references for clone_shared (filled by .random()
@@ -98,13 +103,13 @@ class HIPSliceEngine:
     @classmethod
     def from_ggml(cls, f: ggml.GGMLFile, n_ctx: int = 2048,
                   max_batch: int = 16, gqa_attention: bool = True,
-                  kv_dtype: str = "f16",
-                  kv8_prefill: bool = True) -> "HIPSliceEngine":
+                  kv_dtype: str = "f16", kv8_prefill: bool = True,
+                  kv8_prefix: bool = False) -> "HIPSliceEngine":
         hp = f.hparams
         first = hp.first_layer if hp.first_layer is not None else 0
         eng = cls(hp, hp.n_layer, first, n_ctx, max_batch,
                   gqa_attention=gqa_attention, kv_dtype=kv_dtype,
-                  kv8_prefill=kv8_prefill)
+                  kv8_prefill=kv8_prefill, kv8_prefix=kv8_prefix)
         eng.load_layers(f)
         return eng
 
@@ -114,7 +119,8 @@ class HIPSliceEngine:
                with_extra: bool = True,
                max_prefill: Optional[int] = None,
                gqa_attention: bool = True, kv_dtype: str = "f16",
-               kv8_prefill: bool = True) -> "HIPSliceEngine":
+               kv8_prefill: bool = True,
+               kv8_prefix: bool = False) -> "HIPSliceEngine":
         """Random-init engine straight on the GPU (synthetic benchmarking).
 
         Generates weights directly in the repacked kernel layout — identical
@@ -123,7 +129,8 @@ class HIPSliceEngine:
         """
         eng = cls(hp, n_layers, first_layer, n_ctx, max_batch,
                   max_prefill=max_prefill, gqa_attention=gqa_attention,
-                  kv_dtype=kv_dtype, kv8_prefill=kv8_prefill)
+                  kv_dtype=kv_dtype, kv8_prefill=kv8_prefill,
+                  kv8_prefix=kv8_prefix)
         g = torch.Generator(device="cuda")
         g.manual_seed(seed)
         E, F, V = hp.n_embd, hp.n_ff, hp.n_vocab
@@ -192,7 +199,8 @@ class HIPSliceEngine:
                               max_prefill=int(self._eng.max_prefill),
                               gqa_attention=self.gqa_attention,
                               kv_dtype=self.kv_dtype,
-                              kv8_prefill=self.kv8_prefill)
+                              kv8_prefill=self.kv8_prefill,
+                              kv8_prefix=self.kv8_prefix)
         for li, (an, fn, mats) in enumerate(self._layers_cache):
             twin._eng.set_layer(li, an, fn, mats)
         twin._layers_cache = self._layers_cache  # enables further clones
@@ -441,11 +449,14 @@ class TorchSliceEngine:
     def __init__(self, hp: ggml.Hparams, weights: Dict[str, torch.Tensor],
                  n_layers: int, first_layer: int, n_ctx: int = 512,
                  max_batch: int = 4, device: str = "cpu",
-                 kv_dtype: str = "f16"):
+                 kv_dtype: str = "f16", kv8_prefix: bool = False):
         self.hp = hp
         # "q8": every K/V row is fake-quantised as it is stored
         # (quantize_kv_rows), the CPU twin of the int8 KV cache
         self.kv_dtype = _check_kv_dtype(kv_dtype)
+        # q8 serves prefix= (the cache already holds the fake-quantised
+        # rows); False keeps HIPSliceEngine's default refusal
+        self.kv8_prefix = kv8_prefix
         self.w = weights
         self.first_layer = first_layer
         self.n_layers = n_layers
@@ -462,13 +473,13 @@ class TorchSliceEngine:
 
     @classmethod
     def from_ggml(cls, f: ggml.GGMLFile, n_ctx: int = 512,
-                  max_batch: int = 4,
-                  kv_dtype: str = "f16") -> "TorchSliceEngine":
+                  max_batch: int = 4, kv_dtype: str = "f16",
+                  kv8_prefix: bool = False) -> "TorchSliceEngine":
         from ..models.llama import weights_from_ggml
         hp = f.hparams
         first = hp.first_layer if hp.first_layer is not None else 0
         return cls(hp, weights_from_ggml(f), hp.n_layer, first, n_ctx,
-                   max_batch, kv_dtype=kv_dtype)
+                   max_batch, kv_dtype=kv_dtype, kv8_prefix=kv8_prefix)
 
     def attach_extra(self, f: ggml.GGMLFile) -> None:
         from ..models.llama import weights_from_ggml
@@ -490,7 +501,7 @@ class TorchSliceEngine:
         seq_l = seq.tolist()
         q8 = self.kv_dtype == "q8"
         if prefix is not None:
-            if q8:
+            if q8 and not self.kv8_prefix:
                 raise ValueError("kv_dtype='q8' does not support prefix=")
             pslot, P, pfx = prefix
             pslot, P, pfx_l = int(pslot), int(P), pfx.tolist()
@@ -628,12 +639,15 @@ class TorchSliceEngine:
 
 
 def engine_for_slice(f: ggml.GGMLFile, n_ctx: int, max_batch: int,
-                     device: Optional[str] = None, kv_dtype: str = "f16"):
+                     device: Optional[str] = None, kv_dtype: str = "f16",
+                     kv8_prefix: bool = False):
     """Pick the engine for this machine: HIP when a GPU is present."""
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if device == "cuda":
         return HIPSliceEngine.from_ggml(f, n_ctx=n_ctx, max_batch=max_batch,
-                                        kv_dtype=kv_dtype)
+                                        kv_dtype=kv_dtype,
+                                        kv8_prefix=kv8_prefix)
     return TorchSliceEngine.from_ggml(f, n_ctx=n_ctx, max_batch=max_batch,
-                                      kv_dtype=kv_dtype)
+                                      kv_dtype=kv_dtype,
+                                      kv8_prefix=kv8_prefix)

@@ -1,6 +1,7 @@
 // Int8 KV cache (kv_dtype = "q8", gfx950): the quantising append
 // `k_kv8_append`, the matrix-core attention kernel `k_attn_kv8` over the
-// byte caches and its Q-tiled prefill sibling `k_attn_kv8_prefill`, with
+// byte caches, its Q-tiled prefill sibling `k_attn_kv8_prefill` and the
+// shared-prefix pair `k_attn_kv8_prefix` + `k_attn_kv8_prefix_tail`, with
 // their launchers (formats and semantics: kernels.h).
 //
 // A cache row of one KV head is D bytes u = q + 128, q in [-127, 127], and
@@ -768,6 +769,385 @@ GQA_FN __global__ __launch_bounds__(BLOCK) void k_attn_kv8_prefill(
     }
 }
 
+// ------------------------------------------- shared-prefix attention (q8)
+// launch_attn_prefix's semantics over the byte caches (kv8_prefix): token t
+// attends rows [0, pfx[t]) of slot `pslot`, then rows [pfx[t], pos[t]] of its
+// own slot seq[t]; pfx[t] is 0 or P.
+//
+// k_attn_kv8_prefix covers the prefix rows. It is k_attn_kv8_prefill with one
+// segment, slot pslot, cut into chunks: one block per (16-token tile, query
+// head, prefix chunk [cs, ce)), the tile's tokens as the MFMA columns, so a
+// prefix row is read and expanded from bytes once per 16 tokens. The stream
+// is kv8_tile_step_q as it is, with the per-column limit min(pfx[c], ce)
+// (0 past T): a column without a prefix is dead and keeps (m = -inf, l = 0,
+// o = 0, R = 0) for the whole stream. Every sharing column attends every row
+// of every tile of the chunk, so each wave that has a tile has state for it.
+// The epilogue merges the four waves in wave order and always writes the
+// un-normalised partial (m, l, o[D]), o already multiplied by the column's
+// R, to ws [T][H][S][D + 2]; (-inf, 0, 0) for a column without a prefix. A
+// tile with no sharing token writes its empty partials and streams nothing.
+//
+// k_attn_kv8_prefix_tail covers the own rows. It is k_attn_kv8 over the row
+// window [r0, pos[t]] of slot seq[t], r0 = P for a sharing token and 0
+// otherwise: one block per (token, KV head, up to 16 query heads of its
+// group), the heads as columns, kv8_tile_step as it is, all four waves, no
+// split (own spans are short where the prefix is long, and a token that does
+// not share is the rare one). The cache bases are advanced by r0 rows and
+// the loop runs j in [0, J), J = pos[t] + 1 - r0: rows are addressed as
+// r0 + j and masked on j, so r0 need not be a multiple of the tile and the
+// masked rows read row r0, which is inside the window. The epilogue folds,
+// per head, first the ceil(P / chunk) prefix partials in ascending chunk
+// order and then the four waves in wave order, against one common maximum,
+// normalises and stores. Row pos[t] is always in the window: l > 0.
+//
+// MFMA columns are independent and all running state is per column (prefix
+// pass) or wave-uniform and a function of the rows alone (tail: R), so a
+// token's bits depend on neither its tile mates, its column, the other
+// heads of its group nor, for T <= 64, on T.
+constexpr int KV8P_MIN_CHUNK = 256;  // prefix rows per split (unmeasured)
+constexpr int KV8P_MAX_SPLITS = 8;   // splits of a full context (unmeasured)
+
+int attn_kv8_prefix_chunk(int n_ctx) {
+    const int per = (n_ctx + KV8P_MAX_SPLITS - 1) / KV8P_MAX_SPLITS;
+    return std::max(KV8P_MIN_CHUNK, (per + 63) & ~63);
+}
+
+int attn_kv8_prefix_splits(int n_ctx, int T) {
+    if (T > 64) return 1;  // more than 4 tiles per head fill the chip
+    const int chunk = attn_kv8_prefix_chunk(n_ctx);
+    return (n_ctx + chunk - 1) / chunk;
+}
+
+template <int DC>
+GQA_FN __global__ __launch_bounds__(BLOCK) void k_attn_kv8_prefix(
+    const float* __restrict__ q_buf, const uint8_t* __restrict__ k8,
+    const uint8_t* __restrict__ v8, const __half* __restrict__ k_scale,
+    const __half* __restrict__ v_scale, const int* __restrict__ pfx,
+    float* __restrict__ ws, int pslot, int P, int T, int grp, int E, int Ekv,
+    int D, int n_ctx, int chunk) {
+    constexpr int NSC = DC > 4 ? DC / 4 : 1;
+    constexpr int QW = NSC * 64;        // staged q row, halves
+    const int cs = (int)blockIdx.z * chunk;
+    if (cs >= P) return;                // block-uniform: chunk past the prefix
+    const int ce = min(P, cs + chunk);
+    const int t0 = (int)blockIdx.x * 16;
+    const int h = blockIdx.y;
+    const int H = gridDim.y;
+    const int hk = h / grp;             // GQA kv head
+    const int nq = min(16, T - t0);
+    const int Hkv = Ekv / D;
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = __builtin_amdgcn_readfirstlane(tid / WAVE);  // scalar
+    const int lq = lane & 15;
+    const int lg = lane >> 4;
+
+    // LDS as in k_attn_kv8_prefill
+    constexpr int OSTR = DC * 16 + 4;
+    constexpr int VT_BYTES = NWAVES * 8 * KV8_VSTRIDE * (int)sizeof(uint32_t);
+    constexpr int SC_BYTES = NWAVES * 64 * (int)sizeof(_Float16);
+    constexpr int Q_BYTES = 16 * (QW + 8) * (int)sizeof(_Float16);
+    constexpr int O_BYTES = NWAVES * 16 * OSTR * (int)sizeof(float);
+    constexpr int S_BYTES = VT_BYTES + SC_BYTES + Q_BYTES;
+    constexpr int LDS_BYTES = S_BYTES > O_BYTES ? S_BYTES : O_BYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
+    __shared__ float lds_m[NWAVES][16];
+    __shared__ float lds_l[NWAVES][16];
+    __shared__ int lds_lim[16];         // min(pfx, ce); 0: no prefix, past T
+    uint32_t* vt = reinterpret_cast<uint32_t*>(lds_raw) +
+                   wid * 8 * KV8_VSTRIDE;
+    _Float16* st = reinterpret_cast<_Float16*>(lds_raw + VT_BYTES) + wid * 64;
+    _Float16 (*lds_q)[QW + 8] = reinterpret_cast<_Float16 (*)[QW + 8]>(
+        lds_raw + VT_BYTES + SC_BYTES);
+    float* lds_o = reinterpret_cast<float*>(lds_raw);
+
+    if (tid < 16) {
+        const bool ok = tid < nq;
+        lds_lim[tid] = ok ? min(pfx[t0 + (ok ? tid : 0)], ce) : 0;
+    }
+    gqa_block_sync();
+    int nact = 0;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) nact += lds_lim[c] > 0 ? 1 : 0;
+
+    if (nact > 0) {                     // block-uniform
+        // Q tile -> LDS as plain f16, zero past D and past T (the factor
+        // does the masking). 1/sqrt(D) joins the K scale.
+        {
+            const float* qt = q_buf + (size_t)t0 * E + (size_t)h * D;
+#pragma unroll
+            for (int i = 0; i < 16 * QW / BLOCK; ++i) {
+                const int idx = tid + i * BLOCK;
+                const int col = idx / QW;
+                const int d = idx % QW;
+                const bool ok = col < nq && d < D;
+                const float v = qt[ok ? (size_t)col * E + d : 0] *
+                                (ok ? 1.0f : 0.0f);
+                lds_q[col][d] = (_Float16)v;
+            }
+        }
+        gqa_block_sync();
+        // score-MFMA B fragments in k_attn_kv8's permuted contraction order
+        ABFrag qf[2 * NSC];
+#pragma unroll
+        for (int c = 0; c < 2 * NSC; ++c) {
+            const uint4 u = *reinterpret_cast<const uint4*>(
+                &lds_q[lq][(c >> 1) * 64 + lg * 16 + (c & 1) * 8]);
+            qf[c].u[0] = u.x; qf[c].u[1] = u.y;
+            qf[c].u[2] = u.z; qf[c].u[3] = u.w;
+        }
+        const float qk_scale = rsqrtf((float)D);
+        const int lim = lds_lim[lq];
+        const size_t row0 = (size_t)pslot * n_ctx;
+        const uint8_t* kb = k8 + row0 * Ekv + hk * D;
+        const uint8_t* vb = v8 + row0 * Ekv + hk * D;
+        const unsigned short* ksb =
+            reinterpret_cast<const unsigned short*>(k_scale) + row0 * Hkv +
+            hk;
+        const unsigned short* vsb =
+            reinterpret_cast<const unsigned short*>(v_scale) + row0 * Hkv +
+            hk;
+
+        float m = -INFINITY, l = 0.0f;  // running state of column lq
+        float R = 0.0f;                 // running max of its rows' V scales
+        f32x4 oacc[DC];
+#pragma unroll
+        for (int dc = 0; dc < DC; ++dc) oacc[dc] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+        // k_attn_kv8's loop over the chunk: wave w streams tiles w, w+4,
+        // ..., two per iteration in two buffers, loads one tile ahead; rows
+        // at or past ce read row 0 of the slot and are above every lim
+        constexpr int STEP = NWAVES * 32;
+        int tj = cs + wid * 32;
+        if (tj < ce) {                  // wave-uniform, scalar
+            Kv8Tile<NSC> cur, alt;
+            kv8_load_tile(cur, kb, vb, ksb, vsb, tj, ce, Ekv, Hkv, D, lane);
+            do {
+                kv8_load_tile(alt, kb, vb, ksb, vsb, tj + STEP, ce, Ekv, Hkv,
+                              D, lane);
+                kv8_tile_step_q<DC, NSC>(cur, qf, vt, st, tj, lim, lane,
+                                         qk_scale, m, l, R, oacc);
+                kv8_load_tile(cur, kb, vb, ksb, vsb, tj + 2 * STEP, ce, Ekv,
+                              Hkv, D, lane);
+                kv8_tile_step_q<DC, NSC>(alt, qf, vt, st, tj + STEP, lim,
+                                         lane, qk_scale, m, l, R, oacc);
+                tj += 2 * STEP;
+            } while (tj < ce);
+        }
+        gqa_block_sync();               // tiles and Q are dead: reuse LDS
+
+        if (lg == 0) {
+            lds_m[wid][lq] = m;
+            lds_l[wid][lq] = l;
+        }
+#pragma unroll
+        for (int dc = 0; dc < DC; ++dc) {
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+                lds_o[(wid * 16 + lq) * OSTR + dc * 16 + lg * 4 + jj] =
+                    oacc[dc][jj] * R;
+        }
+        gqa_block_sync();
+    }
+
+    // thread (col, d mod 16) writes the column's partial: the 4 waves merged
+    // in wave order, or the empty partial
+    const int col = tid >> 4;
+    const int tc = t0 + col;
+    if (tc >= T) return;
+    float* part = ws + (((size_t)tc * H + h) * gridDim.z + blockIdx.z) *
+                           (size_t)(D + 2);
+    if (lds_lim[col] == 0) {
+        if ((tid & 15) == 0) {
+            part[0] = -INFINITY;
+            part[1] = 0.0f;
+        }
+        for (int d = tid & 15; d < D; d += 16) part[2 + d] = 0.0f;
+        return;
+    }
+    float mstar = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) mstar = fmaxf(mstar, lds_m[w][col]);
+    float wsc[NWAVES], lstar = 0.0f;
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) {
+        const float mw = lds_m[w][col];         // -inf: wave had no tile
+        wsc[w] = (mw == -INFINITY) ? 0.0f : __expf(mw - mstar);
+        lstar += lds_l[w][col] * wsc[w];
+    }
+    if ((tid & 15) == 0) {
+        part[0] = mstar;
+        part[1] = lstar;
+    }
+    for (int d = tid & 15; d < D; d += 16) {
+        float ostar = 0.0f;
+#pragma unroll
+        for (int w = 0; w < NWAVES; ++w)
+            ostar += lds_o[(w * 16 + col) * OSTR + d] * wsc[w];
+        part[2 + d] = ostar;
+    }
+}
+
+template <int DC>
+GQA_FN __global__ __launch_bounds__(BLOCK) void k_attn_kv8_prefix_tail(
+    const float* __restrict__ q_buf, const uint8_t* __restrict__ k8,
+    const uint8_t* __restrict__ v8, const __half* __restrict__ k_scale,
+    const __half* __restrict__ v_scale, float* __restrict__ out,
+    unsigned short* __restrict__ out_prep, const int* __restrict__ pos,
+    const int* __restrict__ seq, const int* __restrict__ pfx,
+    const float* __restrict__ ws, int P, int H, int grp, int E, int Ekv,
+    int D, int n_ctx, int jtw, int chunk, int S) {
+    constexpr int NSC = DC > 4 ? DC / 4 : 1;
+    constexpr int QW = NSC * 64;        // staged q row, halves
+    const int t = blockIdx.x;
+    const int r0 = pfx[t] > 0 ? P : 0;
+    const int J = pos[t] + 1 - r0;      // own rows r0 + [0, J), J >= 1
+    const int ntile = (grp + 15) >> 4;  // column tiles per KV head
+    const int hk = (int)blockIdx.y / ntile;
+    const int c0 = ((int)blockIdx.y % ntile) * 16;  // first column's head
+    const int ncol = min(16, grp - c0);
+    const int Hkv = Ekv / D;
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = __builtin_amdgcn_readfirstlane(tid / WAVE);  // scalar
+    const int lq = lane & 15;
+    const int lg = lane >> 4;
+    // bases at row r0 of the slot: j = 0 is the window's first row
+    const size_t row0 = (size_t)seq[t] * n_ctx + r0;
+    const uint8_t* kb = k8 + row0 * Ekv + hk * D;
+    const uint8_t* vb = v8 + row0 * Ekv + hk * D;
+    const unsigned short* ksb =
+        reinterpret_cast<const unsigned short*>(k_scale) + row0 * Hkv + hk;
+    const unsigned short* vsb =
+        reinterpret_cast<const unsigned short*>(v_scale) + row0 * Hkv + hk;
+
+    // LDS as in k_attn_kv8
+    constexpr int OSTR = DC * 16 + 4;
+    constexpr int VT_BYTES = NWAVES * 8 * KV8_VSTRIDE * (int)sizeof(uint32_t);
+    constexpr int SC_BYTES = NWAVES * 64 * (int)sizeof(_Float16);
+    constexpr int Q_BYTES = 16 * (QW + 8) * (int)sizeof(_Float16);
+    constexpr int O_BYTES = NWAVES * 16 * OSTR * (int)sizeof(float);
+    constexpr int S_BYTES = VT_BYTES + SC_BYTES + Q_BYTES;
+    constexpr int LDS_BYTES = S_BYTES > O_BYTES ? S_BYTES : O_BYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
+    __shared__ float lds_m[NWAVES][16];
+    __shared__ float lds_l[NWAVES][16];
+    uint32_t* vt = reinterpret_cast<uint32_t*>(lds_raw) +
+                   wid * 8 * KV8_VSTRIDE;
+    _Float16* st = reinterpret_cast<_Float16*>(lds_raw + VT_BYTES) + wid * 64;
+    _Float16 (*lds_q)[QW + 8] = reinterpret_cast<_Float16 (*)[QW + 8]>(
+        lds_raw + VT_BYTES + SC_BYTES);
+    float* lds_o = reinterpret_cast<float*>(lds_raw);
+
+    // Own spans are short where the prefix is long (one tile per wave or
+    // none), so the kernel is a chain of latencies: the wave's first tile is
+    // requested before the Q tile, and the two round trips overlap. A wave
+    // without a tile (tj >= J) loads row r0 and drops it.
+    constexpr int STEP = NWAVES * 32;
+    int tj = wid * 32;
+    Kv8Tile<NSC> cur, alt;
+    kv8_load_tile(cur, kb, vb, ksb, vsb, tj, J, Ekv, Hkv, D, lane);
+
+    // Q tile -> LDS as f16, zero past D and past the group's last head (the
+    // factor does the masking). 1/sqrt(D) joins the K scale.
+    {
+        const float* qt = q_buf + (size_t)t * E + (size_t)(hk * grp + c0) * D;
+#pragma unroll
+        for (int i = 0; i < 16 * QW / BLOCK; ++i) {
+            const int idx = tid + i * BLOCK;
+            const int col = idx / QW;
+            const int d = idx % QW;
+            const bool ok = col < ncol && d < D;
+            const float v = qt[ok ? col * D + d : 0] * (ok ? 1.0f : 0.0f);
+            lds_q[col][d] = (_Float16)v;
+        }
+    }
+    gqa_block_sync();
+    ABFrag qf[2 * NSC];
+#pragma unroll
+    for (int c = 0; c < 2 * NSC; ++c) {
+        const uint4 u = *reinterpret_cast<const uint4*>(
+            &lds_q[lq][(c >> 1) * 64 + lg * 16 + (c & 1) * 8]);
+        qf[c].u[0] = u.x; qf[c].u[1] = u.y;
+        qf[c].u[2] = u.z; qf[c].u[3] = u.w;
+    }
+    const float qk_scale = rsqrtf((float)D);
+
+    float m = -INFINITY, l = 0.0f;      // running state of column lq
+    float R = 0.0f;                     // running max of the V scales
+    f32x4 oacc[DC];
+#pragma unroll
+    for (int dc = 0; dc < DC; ++dc) oacc[dc] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // k_attn_kv8's loop over j in [0, J): rows at or past J read row r0.
+    // The loads stay unconditional; the step of a tile wholly past J, which
+    // would change nothing (kv8_tile_step), is skipped by a scalar branch.
+    if (tj < J) {                       // wave-uniform, scalar
+        do {
+            kv8_load_tile(alt, kb, vb, ksb, vsb, tj + STEP, J, Ekv, Hkv, D,
+                          lane);
+            kv8_tile_step<DC, NSC>(cur, qf, vt, st, tj, J, lane, qk_scale, m,
+                                   l, R, oacc);
+            kv8_load_tile(cur, kb, vb, ksb, vsb, tj + 2 * STEP, J, Ekv, Hkv,
+                          D, lane);
+            if (tj + STEP < J)
+                kv8_tile_step<DC, NSC>(alt, qf, vt, st, tj + STEP, J, lane,
+                                       qk_scale, m, l, R, oacc);
+            tj += 2 * STEP;
+        } while (tj < J);
+    }
+    gqa_block_sync();                   // tiles and Q are dead: reuse LDS
+
+    if (lg == 0) {
+        lds_m[wid][lq] = m;
+        lds_l[wid][lq] = l;
+    }
+#pragma unroll
+    for (int dc = 0; dc < DC; ++dc) {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+            lds_o[(wid * 16 + lq) * OSTR + dc * 16 + lg * 4 + jj] =
+                oacc[dc][jj] * R;
+    }
+    gqa_block_sync();
+    // thread (col, d mod 16): the prefix partials in ascending chunk order,
+    // then the 4 waves in wave order, against one common maximum
+    const int col = tid >> 4;
+    if (col >= ncol) return;
+    const int h = hk * grp + c0 + col;
+    const int n = r0 > 0 ? (P + chunk - 1) / chunk : 0;     // <= S
+    const float* part = ws + ((size_t)t * H + h) * S * (size_t)(D + 2);
+    float mstar = -INFINITY;
+    for (int i = 0; i < n; ++i)
+        mstar = fmaxf(mstar, part[(size_t)i * (D + 2)]);
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) mstar = fmaxf(mstar, lds_m[w][col]);
+    // mstar is finite (row pos[t]); a sharing token's partials are too
+    float lstar = 0.0f;
+    for (int i = 0; i < n; ++i) {
+        const float* pi = part + (size_t)i * (D + 2);
+        lstar += pi[1] * __expf(pi[0] - mstar);
+    }
+    float wsc[NWAVES];
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) {
+        const float mw = lds_m[w][col];         // -inf: wave had no tile
+        wsc[w] = (mw == -INFINITY) ? 0.0f : __expf(mw - mstar);
+        lstar += lds_l[w][col] * wsc[w];
+    }
+    for (int d = tid & 15; d < D; d += 16) {
+        float num = 0.0f;
+        for (int i = 0; i < n; ++i) {
+            const float* pi = part + (size_t)i * (D + 2);
+            num += pi[2 + d] * __expf(pi[0] - mstar);
+        }
+#pragma unroll
+        for (int w = 0; w < NWAVES; ++w)
+            num += lds_o[(w * 16 + col) * OSTR + d] * wsc[w];
+        gqa_store_out(num / lstar, h * D + d, t, E, jtw, out, out_prep);
+    }
+}
+
 // ============================================================== launchers
 
 void launch_kv8_append(hipStream_t s, const __half* k_stage,
@@ -819,4 +1199,43 @@ void launch_attn_kv8_prefill(hipStream_t s, const float* q_buf,
                        k8_layer, v8_layer, k_scale_layer, v_scale_layer, out,
                        out_prep, pos, seq, T, H / Hkv, E, Ekv, D, n_ctx,
                        jt_width(T));
+}
+
+template <int DC>
+static void kv8_prefix_launch(hipStream_t s, const float* q_buf,
+                              const uint8_t* k8, const uint8_t* v8,
+                              const __half* ksc, const __half* vsc,
+                              float* out, unsigned short* out_prep,
+                              const int* pos, const int* seq, const int* pfx,
+                              int pslot, int P, int T, int H, int Hkv, int E,
+                              int Ekv, int D, int n_ctx, float* ws, int chunk,
+                              int S) {
+    const int grp = H / Hkv;
+    hipLaunchKernelGGL(k_attn_kv8_prefix<DC>, dim3((T + 15) / 16, H, S),
+                       dim3(BLOCK), 0, s, q_buf, k8, v8, ksc, vsc, pfx, ws,
+                       pslot, P, T, grp, E, Ekv, D, n_ctx, chunk);
+    hipLaunchKernelGGL(k_attn_kv8_prefix_tail<DC>,
+                       dim3(T, Hkv * ((grp + 15) / 16)), dim3(BLOCK), 0, s,
+                       q_buf, k8, v8, ksc, vsc, out, out_prep, pos, seq, pfx,
+                       ws, P, H, grp, E, Ekv, D, n_ctx, jt_width(T), chunk,
+                       S);
+}
+
+void launch_attn_kv8_prefix(hipStream_t s, const float* q_buf,
+                            const uint8_t* k8_layer, const uint8_t* v8_layer,
+                            const __half* k_scale_layer,
+                            const __half* v_scale_layer, float* out,
+                            unsigned short* out_prep, const int* pos,
+                            const int* seq, const int* pfx, int pslot, int P,
+                            int T, int H, int Hkv, int E, int Ekv, int D,
+                            int n_ctx, float* ws) {
+    const int S = attn_kv8_prefix_splits(n_ctx, T);
+    // one split covers the whole prefix, whatever its length
+    const int chunk = (S == 1) ? std::max(n_ctx, KV8P_MIN_CHUNK)
+                               : attn_kv8_prefix_chunk(n_ctx);
+    auto fn = D <= 16 ? kv8_prefix_launch<1> : D <= 32 ? kv8_prefix_launch<2>
+            : D <= 64 ? kv8_prefix_launch<4> : kv8_prefix_launch<8>;
+    fn(s, q_buf, k8_layer, v8_layer, k_scale_layer, v_scale_layer, out,
+       out_prep, pos, seq, pfx, pslot, P, T, H, Hkv, E, Ekv, D, n_ctx, ws,
+       chunk, S);
 }

@@ -69,6 +69,15 @@ int64_t kv8_ws_numel(int64_t H, int64_t D, int64_t n_ctx) {
     return (int64_t)kMaxTokens * H * attn_kv8_splits((int)n_ctx, 1) * (D + 2);
 }
 
+// prefix partials of launch_attn_kv8_prefix: prefix_ws_numel's rule at the
+// q8 kernels' own splits
+int64_t kv8_prefix_ws_numel(int64_t H, int64_t D, int64_t n_ctx,
+                            int64_t max_t) {
+    return std::max<int64_t>(
+               (int64_t)kMaxTokens * attn_kv8_prefix_splits((int)n_ctx, 1),
+               max_t) * H * (D + 2);
+}
+
 int64_t slab_numel(int64_t tiles, int64_t ks = kMaxSplit) {
     return tiles * ks * kMaxTokens * 16;
 }
@@ -192,7 +201,8 @@ class SliceEngine {
                 int64_t n_ff, int64_t n_ctx, int64_t max_batch, double eps,
                 double rope_base, int64_t max_prefill = 1024,
                 int64_t n_head_kv = 0, bool gqa_attention = true,
-                int64_t kv_dtype = 0, bool kv8_prefill = true)
+                int64_t kv_dtype = 0, bool kv8_prefill = true,
+                bool kv8_prefix = false)
         : E_((int)n_embd),
           H_((int)n_head),
           D_((int)(n_embd / n_head)),
@@ -203,7 +213,8 @@ class SliceEngine {
           eps_((float)eps),
           gqa_attention_(gqa_attention),
           kv8_(kv_dtype == 1),
-          kv8_prefill_(kv8_prefill) {
+          kv8_prefill_(kv8_prefill),
+          kv8_prefix_(kv8_prefix) {
         TORCH_CHECK(kv_dtype == 0 || kv_dtype == 1,
                     "kv_dtype must be 0 (f16) or 1 (q8)");
         TORCH_CHECK(E_ % H_ == 0, "n_embd not divisible by n_head");
@@ -251,6 +262,9 @@ class SliceEngine {
             k_stage_ = torch::zeros({stage}, f16);
             v_stage_ = torch::zeros({stage}, f16);
             kv8_ws_ = torch::zeros({kv8_ws_numel(H_, D_, ctx_)}, f32);
+            if (kv8_prefix_)  // partials of launch_attn_kv8_prefix
+                kv8_prefix_ws_ = torch::zeros(
+                    {kv8_prefix_ws_numel(H_, D_, ctx_, maxP_)}, f32);
         } else {
             kv_store_k_ = torch::zeros({kv_elems + 16}, f16);
             kv_store_v_ = torch::zeros({kv_elems + 16}, f16);
@@ -360,7 +374,9 @@ class SliceEngine {
     // slot pslot and rows [pfx[t], pos[t]] of its own; pfx[t] is 0 or P and
     // pos[t] >= pfx[t] (the caller's contract, kernels.h). Every T then runs
     // qkv with its finish pass and launch_attn_prefix instead of the routed
-    // attention kernel. None: nothing changes.
+    // attention kernel. None: nothing changes. A q8 engine serves prefix only
+    // when it was built with kv8_prefix: qkv, k_kv8_append, then
+    // launch_attn_kv8_prefix over the byte caches.
     torch::Tensor forward(torch::Tensor x, torch::Tensor pos,
                           torch::Tensor seq, bool decode = false,
                           py::object prefix = py::none()) {
@@ -396,7 +412,7 @@ class SliceEngine {
         float* xp = x.data_ptr<float>();
         const int* pp = pos.data_ptr<int>();
         const int* sp = seq.data_ptr<int>();
-        TORCH_CHECK(!kv8_ || prefix.is_none(),
+        TORCH_CHECK(!kv8_ || kv8_prefix_ || prefix.is_none(),
                     "kv_dtype q8 does not support prefix (shared-prefix "
                     "attention reads an f16 cache)");
         const size_t layer_stride = (size_t)B_ * ctx_ * EK_;
@@ -435,7 +451,7 @@ class SliceEngine {
             pslot = (int)ps;
             plen = (int)pl;
             fp = pfx.data_ptr<int>();
-            if (!prefix_ws_.defined())  // first use
+            if (!kv8_ && !prefix_ws_.defined())  // first use
                 prefix_ws_ = torch::zeros(
                     {prefix_ws_numel(H_, D_, ctx_, maxP_)},
                     torch::TensorOptions().device(torch::kCUDA).dtype(
@@ -515,7 +531,13 @@ class SliceEngine {
                 launch_kv8_append(s, kc, vc, k8, v8, ksc, vsc, pp, sp, T,
                                   HK_, D_, ctx_);
                 ck("kv8 append", li);
-                if (attn_kv8_route(T, decode ? 1 : 0, kv8_prefill_ ? 1 : 0))
+                if (shared)
+                    launch_attn_kv8_prefix(s, qb, k8, v8, ksc, vsc, ab, aprep,
+                                           pp, sp, fp, pslot, plen, T, H_,
+                                           HK_, E_, EK_, D_, ctx_,
+                                           kv8_prefix_ws_.data_ptr<float>());
+                else if (attn_kv8_route(T, decode ? 1 : 0,
+                                        kv8_prefill_ ? 1 : 0))
                     launch_attn_kv8_prefill(s, qb, k8, v8, ksc, vsc, ab,
                                             aprep, pp, sp, T, H_, HK_, E_,
                                             EK_, D_, ctx_);
@@ -796,6 +818,7 @@ class SliceEngine {
     bool gqa_attention_;     // GQA models: route attention to k_attn_gqa
     bool kv8_;               // kv_dtype q8: byte caches, k_attn_kv8
     bool kv8_prefill_;       // q8 prompt spans > 64: k_attn_kv8_prefill
+    bool kv8_prefix_;        // q8 serves prefix: launch_attn_kv8_prefix
     std::vector<Layer> layers_;
     std::vector<bool> loaded_;
     torch::Tensor kv_store_k_, kv_store_v_;
@@ -806,6 +829,7 @@ class SliceEngine {
     torch::Tensor prefix_ws_;  // allocated by the first forward with prefix
     // kv_dtype q8 only: scale planes, single-layer f16 stages, split-KV ws
     torch::Tensor k_scale_, v_scale_, k_stage_, v_stage_, kv8_ws_;
+    torch::Tensor kv8_prefix_ws_;  // kv8_prefix: allocated by the constructor
     // prompt scoring, allocated by the first score() call
     torch::Tensor ss_score_, score_key_, score_sum_, score_tgt_;
     bool has_extra_ = false;
@@ -1064,6 +1088,39 @@ AttnResult attention_kv8_prefill(torch::Tensor q, torch::Tensor k8,
                             u16p(std::get<1>(r)), pos.data_ptr<int>(),
                             seq.data_ptr<int>(), d.T, d.H, d.Hkv, d.E, d.Ekv,
                             d.D, d.ctx);
+    return r;
+}
+
+// k_attn_kv8_prefix + k_attn_kv8_prefix_tail; the partials workspace is per
+// call
+AttnResult attention_kv8_prefix(torch::Tensor q, torch::Tensor k8,
+                                torch::Tensor v8, torch::Tensor k_scale,
+                                torch::Tensor v_scale, torch::Tensor pos,
+                                torch::Tensor seq, torch::Tensor pfx,
+                                int64_t pslot, int64_t P, int64_t n_head,
+                                int64_t n_head_kv, int64_t n_ctx,
+                                int64_t n_slots) {
+    const AttnDims d = check_kv8_args(q, k8, v8, k_scale, v_scale, pos, seq,
+                                      n_head, n_head_kv, n_ctx, n_slots);
+    TORCH_CHECK(pslot >= 0 && pslot < n_slots,
+                "pslot out of [0, n_slots)");
+    TORCH_CHECK(P >= 1 && P < n_ctx, "P out of [1, n_ctx)");
+    check_i32(pfx, "pfx");
+    TORCH_CHECK(pfx.dim() == 1 && pfx.numel() == d.T, "pfx must be [T]");
+    TORCH_CHECK(((pfx == 0) | ((pfx == P) & (pos >= pfx))).all().item<bool>(),
+                "pfx must be 0 or P, and pos >= pfx");
+    AttnResult r = alloc_attn_result(d);
+    auto ws = torch::zeros(
+        {kv8_prefix_ws_numel(d.H, d.D, d.ctx, d.T)},
+        torch::TensorOptions().device(torch::kCUDA).dtype(torch::kFloat32));
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    launch_attn_kv8_prefix(s, q.data_ptr<float>(), k8.data_ptr<uint8_t>(),
+                           v8.data_ptr<uint8_t>(), h16c(k_scale),
+                           h16c(v_scale), std::get<0>(r).data_ptr<float>(),
+                           u16p(std::get<1>(r)), pos.data_ptr<int>(),
+                           seq.data_ptr<int>(), pfx.data_ptr<int>(),
+                           (int)pslot, (int)P, d.T, d.H, d.Hkv, d.E, d.Ekv,
+                           d.D, d.ctx, ws.data_ptr<float>());
     return r;
 }
 
@@ -1475,6 +1532,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("attn_kv8_splits", [](int64_t n_ctx, int64_t T) {
         return (int64_t)attn_kv8_splits((int)n_ctx, (int)T);
     }, py::arg("n_ctx"), py::arg("T"));
+    m.def("attention_kv8_prefix", &attention_kv8_prefix, py::arg("q"),
+          py::arg("k8"), py::arg("v8"), py::arg("k_scale"),
+          py::arg("v_scale"), py::arg("pos"), py::arg("seq"),
+          py::arg("pfx"), py::arg("pslot"), py::arg("P"), py::arg("n_head"),
+          py::arg("n_head_kv"), py::arg("n_ctx"), py::arg("n_slots"));
+    m.def("attn_kv8_prefix_chunk", [](int64_t n_ctx) {
+        return (int64_t)attn_kv8_prefix_chunk((int)n_ctx);
+    }, py::arg("n_ctx"));
+    m.def("attn_kv8_prefix_splits", [](int64_t n_ctx, int64_t T) {
+        return (int64_t)attn_kv8_prefix_splits((int)n_ctx, (int)T);
+    }, py::arg("n_ctx"), py::arg("T"));
     m.def("attn_prefix_chunk", [](int64_t n_ctx) {
         return (int64_t)attn_prefix_chunk((int)n_ctx);
     }, py::arg("n_ctx"));
@@ -1514,13 +1582,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     py::class_<SliceEngine, std::shared_ptr<SliceEngine>>(m, "SliceEngine")
         .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                       double, double, int64_t, int64_t, bool, int64_t,
-                      bool>(),
+                      bool, bool>(),
              py::arg("n_embd"), py::arg("n_head"), py::arg("n_layers"),
              py::arg("n_ff"), py::arg("n_ctx"), py::arg("max_batch"),
              py::arg("eps"), py::arg("rope_base"),
              py::arg("max_prefill") = 1024, py::arg("n_head_kv") = 0,
              py::arg("gqa_attention") = true, py::arg("kv_dtype") = 0,
-             py::arg("kv8_prefill") = true)
+             py::arg("kv8_prefill") = true, py::arg("kv8_prefix") = false)
         .def("set_layer", &SliceEngine::set_layer)
         .def("set_extra", &SliceEngine::set_extra)
         .def("forward", &SliceEngine::forward, py::arg("x"),

@@ -218,6 +218,30 @@ void launch_attn_kv8_prefill(hipStream_t s, const float* q_buf,
                              const int* seq, int T, int H, int Hkv, int E,
                              int Ekv, int D, int n_ctx);
 
+// Shared-prefix attention over the byte caches (kv8_prefix): the semantics
+// and argument contract of launch_attn_prefix below, for 1 <= H/Hkv <= 64.
+// Two launches on one stream, any T:
+//   k_attn_kv8_prefix       one block per (16-token tile, head, prefix
+//                           chunk), the tile's tokens as MFMA columns:
+//                           un-normalised partials ws [T][H][S][D + 2]
+//   k_attn_kv8_prefix_tail  one block per (token, KV head, 16 query heads):
+//                           the own rows [r0, pos[t]] on the matrix cores,
+//                           the prefix partials folded in ascending chunk
+//                           order, then the four waves; out and out_prep
+// attn_kv8_prefix_chunk / _splits follow the GQA rule (functions of n_ctx
+// alone for T <= 64, S = 1 for T > 64). ws holds T * H * S * (D + 2) floats.
+int attn_kv8_prefix_chunk(int n_ctx);
+int attn_kv8_prefix_splits(int n_ctx, int T);
+
+void launch_attn_kv8_prefix(hipStream_t s, const float* q_buf,
+                            const uint8_t* k8_layer, const uint8_t* v8_layer,
+                            const __half* k_scale_layer,
+                            const __half* v_scale_layer, float* out,
+                            unsigned short* out_prep, const int* pos,
+                            const int* seq, const int* pfx, int pslot, int P,
+                            int T, int H, int Hkv, int E, int Ekv, int D,
+                            int n_ctx, float* ws);
+
 // ------------------------------------------------ shared-prefix attention
 // Token t attends rows [0, pfx[t]) of slot `pslot`, then rows
 // [pfx[t], pos[t]] of slot seq[t]. pfx is a device i32 [T] whose entries are

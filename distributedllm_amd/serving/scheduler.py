@@ -146,7 +146,8 @@ class ContinuousBatcher:
                     raise ValueError(
                         "shared_prefix needs an engine whose forward takes "
                         "prefix=")
-                if getattr(e, "kv_dtype", "f16") != "f16":
+                if (getattr(e, "kv_dtype", "f16") != "f16" and
+                        not getattr(e, "kv8_prefix", False)):
                     raise ValueError(
                         "shared_prefix and kv_dtype='q8' cannot be combined: "
                         "shared-prefix attention reads an f16 KV cache")

@@ -71,6 +71,9 @@ def main():
                          "batcher is not told (every request prefills and "
                          "attends its own copy) - the baseline of the "
                          "comparison")
+    ap.add_argument("--kv-dtype", choices=["f16", "q8"], default="f16",
+                    help="KV cache element type; q8 with prefix sharing "
+                         "builds the engine with kv8_prefix")
     args = ap.parse_args()
     if args.device_sampling and args.temperature is None:
         ap.error("--device-sampling needs --temperature")
@@ -80,7 +83,8 @@ def main():
     # sharing reserves one KV slot per lane: --slots stay usable
     eng = HIPSliceEngine.random(hp, n_layers=hp.n_layer, n_ctx=args.ctx,
                                 max_batch=args.slots + (1 if share else 0),
-                                with_extra=True)
+                                with_extra=True, kv_dtype=args.kv_dtype,
+                                kv8_prefix=share and args.kv_dtype == "q8")
     lanes = None
     if args.lanes > 1:
         lanes = [eng] + [eng.clone_shared()
@@ -163,7 +167,8 @@ def main():
           f"p95={p(0.95):.2f}s max={lat[-1]:.2f}s")
     if args.shared_prefix:
         dd = sorted(decode) or [float("nan")]
-        print(f"shared prefix {args.shared_prefix} tokens, sharing "
+        print(f"kv {args.kv_dtype}, "
+              f"shared prefix {args.shared_prefix} tokens, sharing "
               f"{'on' if share else 'off'}: {len(admit)} admitting steps "
               f"(admission + one decode each) {sum(admit)*1e3:.1f} ms in "
               f"all; decode-only steps p50={dd[len(dd)//2]*1e3:.2f} ms "
