@@ -316,6 +316,7 @@ class BatchGenerateCommand(Command):
         p.add_argument("--ctx", type=int, default=2048)
         p.add_argument("--kv-dtype", choices=["f16", "q8"], default="f16",
                        help=_KV_DTYPE_HELP)
+        _add_kv_layout_args(p)
         p.add_argument("--temp", type=float, default=0.7)
         p.add_argument("--rp", type=float, default=1.1)
         p.add_argument("--greedy", action="store_true")
@@ -357,7 +358,9 @@ class BatchGenerateCommand(Command):
         extra = 1 if args.shared_prefix_file else 0
         eng = engine_for_slice(f, n_ctx=args.ctx, max_batch=n_slots + extra,
                                kv_dtype=args.kv_dtype,
-                               kv8_prefix=_wants_kv8_prefix(args))
+                               kv8_prefix=_wants_kv8_prefix(args),
+                               kv_layout=args.kv_layout,
+                               kv_pages=args.kv_pages)
         eng.attach_extra(slicer.make_extra_layers(f))
         tok = Tokenizer(f.vocab)
         prefix = _read_shared_prefix(args.shared_prefix_file, tok)
@@ -422,6 +425,19 @@ _KV_DTYPE_HELP = (
     "as bytes too")
 
 
+def _add_kv_layout_args(p: argparse.ArgumentParser) -> None:
+    p.add_argument("--kv-layout", choices=["contiguous", "paged"],
+                   default="contiguous",
+                   help="paged: the KV cache is a pool of 16-row pages and a "
+                        "request holds only the pages its prompt + new "
+                        "tokens need, instead of a whole n_ctx slot (f16 "
+                        "only, no --shared-prefix-file)")
+    p.add_argument("--kv-pages", type=int, default=None, metavar="N",
+                   help="pages in the pool of a paged KV cache, per lane "
+                        "(default: slots * ceil(ctx / 16) + 1, the "
+                        "contiguous capacity)")
+
+
 def _wants_kv8_prefix(args) -> bool:
     """q8 engines serve a shared prefix only when built with kv8_prefix:
     both options together switch it on."""
@@ -457,6 +473,7 @@ class ServeHttpCommand(Command):
         p.add_argument("--ctx", type=int, default=2048)
         p.add_argument("--kv-dtype", choices=["f16", "q8"], default="f16",
                        help=_KV_DTYPE_HELP)
+        _add_kv_layout_args(p)
         p.add_argument("--prefill-chunk", type=int, default=64,
                        help="max prompt tokens prefilled per lane per "
                             "decode step (latency fairness; 0 = "
@@ -514,7 +531,9 @@ class ServeHttpCommand(Command):
                 n_lanes = min(5, fit) if fit >= 3 else 1
         eng = engine_for_slice(f, n_ctx=args.ctx, max_batch=args.slots,
                                kv_dtype=args.kv_dtype,
-                               kv8_prefix=_wants_kv8_prefix(args))
+                               kv8_prefix=_wants_kv8_prefix(args),
+                               kv_layout=args.kv_layout,
+                               kv_pages=args.kv_pages)
         eng.attach_extra(slicer.make_extra_layers(f))
         lanes = None
         if n_lanes > 1 and hasattr(eng, "clone_shared"):

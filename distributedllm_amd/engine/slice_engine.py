@@ -30,6 +30,8 @@ from .repack import (W_F32, _BYTE_GTYPES, _upload_mat, random_tiles,
 from .sampler import LOGPROBS_MAX_TOP
 
 KV_DTYPES = ("f16", "q8")
+KV_LAYOUTS = ("contiguous", "paged")
+KV_PAGE_ROWS = 16   # rows per KV page (ops/csrc/attention_paged.hip)
 
 
 def _check_kv_dtype(kv_dtype: str) -> str:
@@ -37,6 +39,13 @@ def _check_kv_dtype(kv_dtype: str) -> str:
         raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, "
                          f"got {kv_dtype!r}")
     return kv_dtype
+
+
+def _check_kv_layout(kv_layout: str) -> str:
+    if kv_layout not in KV_LAYOUTS:
+        raise ValueError(f"kv_layout must be one of {KV_LAYOUTS}, "
+                         f"got {kv_layout!r}")
+    return kv_layout
 
 
 def quantize_kv_rows(x: torch.Tensor) -> torch.Tensor:
@@ -59,7 +68,9 @@ class HIPSliceEngine:
                  n_ctx: int = 2048, max_batch: int = 16,
                  max_prefill: Optional[int] = None,
                  gqa_attention: bool = True, kv_dtype: str = "f16",
-                 kv8_prefill: bool = True, kv8_prefix: bool = False):
+                 kv8_prefill: bool = True, kv8_prefix: bool = False,
+                 kv_layout: str = "contiguous",
+                 kv_pages: Optional[int] = None):
         from .. import ops
         core = ops.core()
         self.hp = hp
@@ -80,6 +91,28 @@ class HIPSliceEngine:
         # q8 serves prefix= on k_attn_kv8_prefix + k_attn_kv8_prefix_tail;
         # False keeps the refusal
         self.kv8_prefix = kv8_prefix
+        # "paged": per layer one pool of kv_pages 16-row pages instead of
+        # max_batch slots of n_ctx rows; a slot owns only the pages that
+        # kv_reserve gave it, attention on k_attn_paged. f16 only, no prefix=.
+        # The default pool has today's capacity (+ the scratch page 0).
+        self.kv_layout = _check_kv_layout(kv_layout)
+        paged = kv_layout == "paged"
+        if paged and self.kv_dtype != "f16":
+            raise ValueError("kv_layout='paged' and kv_dtype='q8' cannot be "
+                             "combined: the page pools are f16")
+        if not paged and kv_pages is not None:
+            raise ValueError("kv_pages needs kv_layout='paged'")
+        self._slot_pages_max = -(-n_ctx // KV_PAGE_ROWS)
+        if paged and kv_pages is None:
+            kv_pages = max_batch * self._slot_pages_max + 1
+        if paged and kv_pages < 2:
+            raise ValueError("kv_pages must be >= 2 (page 0 is the scratch "
+                             "page)")
+        self.kv_pages = int(kv_pages) if paged else 0
+        # host-side free list (page 0 is never handed out) and the pages
+        # each slot holds, in row order: the block table's host copy
+        self._free_pages = list(range(self.kv_pages - 1, 0, -1))
+        self._slot_pages = [[] for _ in range(max_batch)]
         # prefill token cap per forward call (side channels scale with it;
         # larger prompts tile host-side in max_prefill chunks)
         if max_prefill is None:
@@ -91,7 +124,8 @@ class HIPSliceEngine:
             n_head_kv=hp.kv_heads if hp.is_gqa else 0,
             gqa_attention=gqa_attention,
             kv_dtype=KV_DTYPES.index(kv_dtype), kv8_prefill=kv8_prefill,
-            kv8_prefix=kv8_prefix)
+            kv8_prefix=kv8_prefix, kv_layout=KV_LAYOUTS.index(kv_layout),
+            kv_pages=self.kv_pages)
         self.device = "cuda"
         self.has_extra = False
         # weight-tensor references for clone_shared (filled by .random()
@@ -104,12 +138,14 @@ class HIPSliceEngine:
     def from_ggml(cls, f: ggml.GGMLFile, n_ctx: int = 2048,
                   max_batch: int = 16, gqa_attention: bool = True,
                   kv_dtype: str = "f16", kv8_prefill: bool = True,
-                  kv8_prefix: bool = False) -> "HIPSliceEngine":
+                  kv8_prefix: bool = False, kv_layout: str = "contiguous",
+                  kv_pages: Optional[int] = None) -> "HIPSliceEngine":
         hp = f.hparams
         first = hp.first_layer if hp.first_layer is not None else 0
         eng = cls(hp, hp.n_layer, first, n_ctx, max_batch,
                   gqa_attention=gqa_attention, kv_dtype=kv_dtype,
-                  kv8_prefill=kv8_prefill, kv8_prefix=kv8_prefix)
+                  kv8_prefill=kv8_prefill, kv8_prefix=kv8_prefix,
+                  kv_layout=kv_layout, kv_pages=kv_pages)
         eng.load_layers(f)
         return eng
 
@@ -119,8 +155,9 @@ class HIPSliceEngine:
                with_extra: bool = True,
                max_prefill: Optional[int] = None,
                gqa_attention: bool = True, kv_dtype: str = "f16",
-               kv8_prefill: bool = True,
-               kv8_prefix: bool = False) -> "HIPSliceEngine":
+               kv8_prefill: bool = True, kv8_prefix: bool = False,
+               kv_layout: str = "contiguous",
+               kv_pages: Optional[int] = None) -> "HIPSliceEngine":
         """Random-init engine straight on the GPU (synthetic benchmarking).
 
         Generates weights directly in the repacked kernel layout — identical
@@ -130,7 +167,8 @@ class HIPSliceEngine:
         eng = cls(hp, n_layers, first_layer, n_ctx, max_batch,
                   max_prefill=max_prefill, gqa_attention=gqa_attention,
                   kv_dtype=kv_dtype, kv8_prefill=kv8_prefill,
-                  kv8_prefix=kv8_prefix)
+                  kv8_prefix=kv8_prefix, kv_layout=kv_layout,
+                  kv_pages=kv_pages)
         g = torch.Generator(device="cuda")
         g.manual_seed(seed)
         E, F, V = hp.n_embd, hp.n_ff, hp.n_vocab
@@ -189,7 +227,8 @@ class HIPSliceEngine:
 
     def clone_shared(self) -> "HIPSliceEngine":
         """A second engine over the SAME weight tensors (HBM shared) with
-        its own KV cache and side-channel buffers — lets independent
+        its own KV cache (paged: its own pool, table and free list of the
+        same size) and side-channel buffers — lets independent
         micro-batches run concurrently on separate HIP streams without
         duplicating the model."""
         assert getattr(self, "_layers_cache", None) is not None, \
@@ -200,7 +239,9 @@ class HIPSliceEngine:
                               gqa_attention=self.gqa_attention,
                               kv_dtype=self.kv_dtype,
                               kv8_prefill=self.kv8_prefill,
-                              kv8_prefix=self.kv8_prefix)
+                              kv8_prefix=self.kv8_prefix,
+                              kv_layout=self.kv_layout,
+                              kv_pages=self.kv_pages or None)
         for li, (an, fn, mats) in enumerate(self._layers_cache):
             twin._eng.set_layer(li, an, fn, mats)
         twin._layers_cache = self._layers_cache  # enables further clones
@@ -242,11 +283,58 @@ class HIPSliceEngine:
         self._eng.set_extra(*self._extra_cache)
         self.has_extra = True
 
+    # ---- paged KV cache: host-side page allocator ----
+
+    @property
+    def kv_free_pages(self) -> int:
+        """Pages nobody holds (0 on a contiguous engine)."""
+        return len(self._free_pages)
+
+    def kv_pages_for(self, n_rows: int) -> int:
+        """Pages that rows [0, n_rows) of one slot occupy."""
+        return -(-int(n_rows) // KV_PAGE_ROWS)
+
+    def kv_reserve(self, slot: int, n_rows: int) -> bool:
+        """Extend `slot`'s pages to cover rows [0, n_rows): True, or False
+        with nothing changed when the pool is short. The new table entries
+        go to the device in one small copy on the current stream (call it
+        outside any graph capture). A forward may only touch rows that are
+        covered. Contiguous engines own all their rows: always True."""
+        if self.kv_layout != "paged":
+            return True
+        if not 0 <= slot < self.max_batch or not 0 <= n_rows <= self.n_ctx:
+            raise ValueError("kv_reserve: slot or row count out of range")
+        have = self._slot_pages[slot]
+        need = self.kv_pages_for(n_rows) - len(have)
+        if need <= 0:
+            return True
+        if need > len(self._free_pages):
+            return False
+        new = [self._free_pages.pop() for _ in range(need)]
+        self._eng.block_table[slot, len(have):len(have) + need].copy_(
+            torch.tensor(new, dtype=torch.int32))
+        have += new
+        return True
+
+    def kv_release(self, slot: int) -> None:
+        """Return `slot`'s pages to the pool and point its table row back at
+        the scratch page. Work already queued on other streams that reads
+        the slot must have been ordered before the pages are reused."""
+        if self.kv_layout != "paged" or not self._slot_pages[slot]:
+            return
+        pages = self._slot_pages[slot]
+        self._eng.block_table[slot, :len(pages)].zero_()
+        self._free_pages.extend(reversed(pages))
+        self._slot_pages[slot] = []
+
     def forward(self, x: torch.Tensor, pos: torch.Tensor,
                 seq: torch.Tensor, decode: bool = False,
                 prefix=None) -> torch.Tensor:
         """decode=True asserts every token is a distinct sequence
         (batched decode) — enables the qkv-slab + fused-attention path.
+
+        kv_layout="paged": every (seq[t], pos[t]) must lie in rows that
+        `kv_reserve` covered; prefix= is refused.
 
         prefix=(pslot, P, pfx): shared-prefix attention. Token t attends
         rows [0, pfx[t]) of KV slot `pslot` followed by rows
@@ -640,14 +728,21 @@ class TorchSliceEngine:
 
 def engine_for_slice(f: ggml.GGMLFile, n_ctx: int, max_batch: int,
                      device: Optional[str] = None, kv_dtype: str = "f16",
-                     kv8_prefix: bool = False):
-    """Pick the engine for this machine: HIP when a GPU is present."""
+                     kv8_prefix: bool = False,
+                     kv_layout: str = "contiguous",
+                     kv_pages: Optional[int] = None):
+    """Pick the engine for this machine: HIP when a GPU is present. The KV
+    layout changes no result, so the CPU twin has none: kv_layout and
+    kv_pages are checked and otherwise ignored there."""
+    _check_kv_layout(kv_layout)
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if device == "cuda":
         return HIPSliceEngine.from_ggml(f, n_ctx=n_ctx, max_batch=max_batch,
                                         kv_dtype=kv_dtype,
-                                        kv8_prefix=kv8_prefix)
+                                        kv8_prefix=kv8_prefix,
+                                        kv_layout=kv_layout,
+                                        kv_pages=kv_pages)
     return TorchSliceEngine.from_ggml(f, n_ctx=n_ctx, max_batch=max_batch,
                                       kv_dtype=kv_dtype,
                                       kv8_prefix=kv8_prefix)

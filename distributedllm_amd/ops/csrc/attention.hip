@@ -283,12 +283,6 @@ __global__ void k_attention(
 // segment separately (causality per token via its own pos, exactly like
 // k_attention). (The VALU kernel this replaced measured ~25x off the
 // issue roofline — 16x16 tiles of dot products belong on MFMA.)
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-
-union BFrag4 {
-    uint32_t u[2];
-    f16x4 v;
-};
 
 // 8 halves [d0, d0+8) of `row`, zero-padded past D
 __device__ __forceinline__ f16x8 load_kfrag8(const __half* __restrict__ row,
@@ -521,7 +515,6 @@ __global__ __launch_bounds__(BLOCK) void k_attn_prefill_mfma(
 
 constexpr int GQA_MIN_CHUNK = 256;  // rows per split, lower bound (unmeasured)
 constexpr int GQA_MAX_SPLITS = 8;   // splits of a full context (unmeasured)
-constexpr int GQA_VSTRIDE = 132;    // 8-byte fragments per j-quad of a V tile
 
 int attn_gqa_chunk(int n_ctx) {
     const int per = (n_ctx + GQA_MAX_SPLITS - 1) / GQA_MAX_SPLITS;
@@ -540,14 +533,9 @@ int attn_route(int H, int Hkv, int T, int decode, int gqa_attention) {
     return (gqa_attention && grp >= 2 && grp <= 64) ? 2 : 0;
 }
 
-// One 16-row KV tile as loaded: K in score-A order (lane: row lq, 8 d of
-// each 32-d chunk), V row-major (lane: rows lg*4 + e, d-octet lq).
-template <int NKC>
-struct GqaTile {
-    uint4 k[NKC];
-    uint4 v[4];
-};
-
+// GqaTile, gqa_stage_v and gqa_tile_step: attn_common.h (shared with
+// attention_paged.hip).
+//
 // Sixteen-byte loads with no branch around them, so that the compiler can
 // keep the next tile's loads in flight behind the current tile's (vmcnt
 // counts only straight-line loads). The scheduling barrier at the end pins
@@ -576,100 +564,6 @@ GQA_FN __device__ __forceinline__ void gqa_load_tile(
         t.v[e] = *reinterpret_cast<const uint4*>(vrow + dv);
     }
     __builtin_amdgcn_sched_barrier(0);
-}
-
-// V transpose. The lane holds V[lg*4 + e][lq*8 + i] (e = 0..3, i = 0..7).
-// It regroups them in registers into the eight PV A fragments of its
-// columns, frag(d) = {V[lg*4 + 0..3][d]}, and writes those 64 contiguous
-// bytes (4 x 16 B) to the wave's tile at [lg][d]; the consumer lane
-// (lq, lg) of d-chunk dc then reads frag(dc*16 + lq) as one 8-byte load,
-// 16 lanes on consecutive addresses. GQA_VSTRIDE pads the lg planes by 8
-// banks so the four planes of one write do not collide.
-GQA_FN __device__ __forceinline__ void gqa_stage_v(
-    uint2* __restrict__ vt, const uint4 v[4], int lq, int lg) {
-    const uint32_t r0[4] = {v[0].x, v[0].y, v[0].z, v[0].w};
-    const uint32_t r1[4] = {v[1].x, v[1].y, v[1].z, v[1].w};
-    const uint32_t r2[4] = {v[2].x, v[2].y, v[2].z, v[2].w};
-    const uint32_t r3[4] = {v[3].x, v[3].y, v[3].z, v[3].w};
-    uint4* dst = reinterpret_cast<uint4*>(vt + lg * GQA_VSTRIDE + lq * 8);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        uint4 o;
-        o.x = (r0[w] & 0xffffu) | (r1[w] << 16);           // d = 2w
-        o.y = (r2[w] & 0xffffu) | (r3[w] << 16);
-        o.z = (r0[w] >> 16) | (r1[w] & 0xffff0000u);       // d = 2w + 1
-        o.w = (r2[w] >> 16) | (r3[w] & 0xffff0000u);
-        dst[w] = o;
-    }
-}
-
-// One 16-row tile of one wave: scores, online softmax on the score C layout,
-// V transpose, PV. (m, l) are the running max and sum of column lq.
-template <int DC, int NKC>
-GQA_FN __device__ __forceinline__ void gqa_tile_step(
-    const GqaTile<NKC>& tile, const ABFrag (&qf)[NKC], uint2* vt, int tj,
-    int ce, int lane, float& m, float& l, f32x4 (&oacc)[DC]) {
-    const int lq = lane & 15;
-    const int lg = lane >> 4;
-    f32x4 sc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < NKC; ++c) {
-        ABFrag kf;
-        kf.u[0] = tile.k[c].x; kf.u[1] = tile.k[c].y;
-        kf.u[2] = tile.k[c].z; kf.u[3] = tile.k[c].w;
-        sc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf.v, qf[c].v, sc,
-                                                    0, 0, 0);
-    }
-    gqa_stage_v(vt, tile.v, lq, lg);
-
-    // lane holds s[j = tj + lg*4 + jj][column lq]
-    float s[4], tm = -INFINITY;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-        s[jj] = (tj + lg * 4 + jj < ce) ? sc[jj] : -INFINITY;
-        tm = fmaxf(tm, s[jj]);
-    }
-    tm = fmaxf(tm, gqa_shfl_xor(tm, lane, 16));
-    tm = fmaxf(tm, gqa_shfl_xor(tm, lane, 32));
-    // finite: the wave's first tile has an attended row. A tile wholly past
-    // the chunk (tm = -inf) leaves m, l and oacc as they are.
-    const float m_new = fmaxf(m, tm);
-    const float alpha = __expf(m - m_new);  // 0 on the first tile
-    float pv[4], ts = 0.0f;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-        pv[jj] = __expf(s[jj] - m_new);     // 0 for masked rows
-        ts += pv[jj];
-    }
-    BFrag4 p;
-    p.u[0] = gqa_pack_f16(pv[0], pv[1]);
-    p.u[1] = gqa_pack_f16(pv[2], pv[3]);
-    ts += gqa_shfl_xor(ts, lane, 16);
-    ts += gqa_shfl_xor(ts, lane, 32);
-    l = l * alpha + ts;
-    m = m_new;
-
-    gqa_wave_sync();                        // V tile written -> read
-    BFrag4 vf[DC];
-#pragma unroll
-    for (int dc = 0; dc < DC; ++dc) {
-        const uint2 u = vt[lg * GQA_VSTRIDE + dc * 16 + lq];
-        vf[dc].u[0] = u.x; vf[dc].u[1] = u.y;
-    }
-    // the accumulators leave the MFMA register file only when some column's
-    // max rose (wave-uniform branch; x * 1 is x)
-    if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
-#pragma unroll
-        for (int dc = 0; dc < DC; ++dc) {
-            oacc[dc][0] *= alpha; oacc[dc][1] *= alpha;
-            oacc[dc][2] *= alpha; oacc[dc][3] *= alpha;
-        }
-    }
-#pragma unroll
-    for (int dc = 0; dc < DC; ++dc)
-        oacc[dc] = __builtin_amdgcn_mfma_f32_16x16x16f16(
-            vf[dc].v, p.v, oacc[dc], 0, 0, 0);
-    gqa_wave_sync();                        // read -> next tile's write
 }
 
 // DC = 16-wide d chunks of the PV product, a power of two >= D/16; the

@@ -78,6 +78,14 @@ int64_t kv8_prefix_ws_numel(int64_t H, int64_t D, int64_t n_ctx,
                max_t) * H * (D + 2);
 }
 
+// split-KV partials of launch_attn_paged: the same layout at its own splits
+int64_t paged_ws_numel(int64_t H, int64_t D, int64_t n_ctx) {
+    return (int64_t)kMaxTokens * H * attn_paged_splits((int)n_ctx, 1) *
+           (D + 2);
+}
+// k_attn_paged keeps ceil(chunk / 16) page ids in LDS
+constexpr int64_t kPagedMaxCtx = 65536;
+
 int64_t slab_numel(int64_t tiles, int64_t ks = kMaxSplit) {
     return tiles * ks * kMaxTokens * 16;
 }
@@ -202,7 +210,8 @@ class SliceEngine {
                 double rope_base, int64_t max_prefill = 1024,
                 int64_t n_head_kv = 0, bool gqa_attention = true,
                 int64_t kv_dtype = 0, bool kv8_prefill = true,
-                bool kv8_prefix = false)
+                bool kv8_prefix = false, int64_t kv_layout = 0,
+                int64_t kv_pages = 0)
         : E_((int)n_embd),
           H_((int)n_head),
           D_((int)(n_embd / n_head)),
@@ -214,9 +223,22 @@ class SliceEngine {
           gqa_attention_(gqa_attention),
           kv8_(kv_dtype == 1),
           kv8_prefill_(kv8_prefill),
-          kv8_prefix_(kv8_prefix) {
+          kv8_prefix_(kv8_prefix),
+          paged_(kv_layout == 1),
+          pages_(kv_pages) {
         TORCH_CHECK(kv_dtype == 0 || kv_dtype == 1,
                     "kv_dtype must be 0 (f16) or 1 (q8)");
+        TORCH_CHECK(kv_layout == 0 || kv_layout == 1,
+                    "kv_layout must be 0 (contiguous) or 1 (paged)");
+        TORCH_CHECK(!paged_ || !kv8_,
+                    "kv_layout paged holds an f16 cache: it cannot be "
+                    "combined with kv_dtype q8");
+        TORCH_CHECK(!paged_ || (kv_pages >= 2 &&
+                                kv_pages * kv_page_rows() <= INT32_MAX),
+                    "kv_layout paged needs kv_pages >= 2 (page 0 is the "
+                    "scratch page), got kv_pages = ", kv_pages);
+        TORCH_CHECK(!paged_ || n_ctx <= kPagedMaxCtx,
+                    "kv_layout paged serves n_ctx <= ", kPagedMaxCtx);
         TORCH_CHECK(E_ % H_ == 0, "n_embd not divisible by n_head");
         TORCH_CHECK(D_ % 2 == 0, "head_dim must be even for RoPE pairs");
         TORCH_CHECK(D_ <= 128, "head_dim > 128 unsupported (the "
@@ -231,6 +253,8 @@ class SliceEngine {
                     "kv_dtype q8 needs head_dim % 4 == 0");
         TORCH_CHECK(!kv8_ || H_ / HK_ <= 64,
                     "kv_dtype q8 serves n_head / n_head_kv <= 64");
+        TORCH_CHECK(!paged_ || H_ / HK_ <= 64,
+                    "kv_layout paged serves n_head / n_head_kv <= 64");
         // prefill token cap per forward call: side channels and q/attn
         // buffers scale with it (a few hundred MB at 2048 on 65B shapes)
         maxP_ = std::max((int)max_prefill, kMaxTokens);
@@ -251,7 +275,21 @@ class SliceEngine {
         // [L, B, ctx, Hkv], one single-layer f16 stage per K and V that the
         // qkv kernels write and k_kv8_append quantises, and the split-KV
         // workspace of k_attn_kv8.
-        const int64_t kv_elems = (int64_t)L_ * B_ * ctx_ * EK_;
+        // kv_layout paged (attention_paged.hip): per layer one pool of
+        // kv_pages 16-row pages instead of B slots of ctx rows, the block
+        // table i32 [B, ceil(ctx / 16)] shared by the layers (all 0: the
+        // scratch page), the kv_row buffer of k_paged_rows and the split-KV
+        // workspace of k_attn_paged.
+        const int64_t kv_rows = paged_ ? pages_ * kv_page_rows()
+                                       : (int64_t)B_ * ctx_;
+        const int64_t kv_elems = (int64_t)L_ * kv_rows * EK_;
+        if (paged_) {
+            auto i32 = dev.dtype(torch::kInt32);
+            const int64_t npg = (ctx_ + kv_page_rows() - 1) / kv_page_rows();
+            table_ = torch::zeros({B_, npg}, i32);
+            kv_row_ = torch::zeros({maxP_}, i32);
+            paged_ws_ = torch::zeros({paged_ws_numel(H_, D_, ctx_)}, f32);
+        }
         if (kv8_) {
             auto u8 = dev.dtype(torch::kUInt8);
             kv_store_k_ = torch::full({kv_elems + 16}, 128, u8);
@@ -269,10 +307,12 @@ class SliceEngine {
             kv_store_k_ = torch::zeros({kv_elems + 16}, f16);
             kv_store_v_ = torch::zeros({kv_elems + 16}, f16);
         }
-        k_cache_ = kv_store_k_.narrow(0, 0, kv_elems)
-                       .view({L_, B_, ctx_, EK_});
-        v_cache_ = kv_store_v_.narrow(0, 0, kv_elems)
-                       .view({L_, B_, ctx_, EK_});
+        // paged: [L, kv_pages * 16, Ekv]
+        const std::vector<int64_t> kv_shape =
+            paged_ ? std::vector<int64_t>{L_, kv_rows, EK_}
+                   : std::vector<int64_t>{L_, B_, ctx_, EK_};
+        k_cache_ = kv_store_k_.narrow(0, 0, kv_elems).view(kv_shape);
+        v_cache_ = kv_store_v_.narrow(0, 0, kv_elems).view(kv_shape);
         // RoPE pair frequencies: theta_i = pos * base^(-2i/D)
         inv_freq_ = torch::pow(
             (float)rope_base,
@@ -321,6 +361,8 @@ class SliceEngine {
                     "the legacy f32 path does not support GQA");
         TORCH_CHECK(l.mfma || !kv8_,
                     "the legacy f32 path does not support kv_dtype q8");
+        TORCH_CHECK(l.mfma || !paged_,
+                    "the legacy f32 path does not support kv_layout paged");
         DevMat* slots[7] = {&l.wq, &l.wk, &l.wv, &l.wo, &l.w1, &l.w2, &l.w3};
         DevMat2* slots2[7] = {&l.mq, &l.mk, &l.mv, &l.mo, &l.m1, &l.m2,
                               &l.m3};
@@ -376,7 +418,11 @@ class SliceEngine {
     // qkv with its finish pass and launch_attn_prefix instead of the routed
     // attention kernel. None: nothing changes. A q8 engine serves prefix only
     // when it was built with kv8_prefix: qkv, k_kv8_append, then
-    // launch_attn_kv8_prefix over the byte caches.
+    // launch_attn_kv8_prefix over the byte caches. A paged engine runs
+    // k_paged_rows once, then per layer qkv (with its finish pass, writing
+    // straight into the pools through kv_row) and launch_attn_paged at every
+    // T; it refuses prefix. The caller keeps the block table covering every
+    // (seq[t], pos[t]) of the call.
     torch::Tensor forward(torch::Tensor x, torch::Tensor pos,
                           torch::Tensor seq, bool decode = false,
                           py::object prefix = py::none()) {
@@ -415,7 +461,12 @@ class SliceEngine {
         TORCH_CHECK(!kv8_ || kv8_prefix_ || prefix.is_none(),
                     "kv_dtype q8 does not support prefix (shared-prefix "
                     "attention reads an f16 cache)");
-        const size_t layer_stride = (size_t)B_ * ctx_ * EK_;
+        TORCH_CHECK(!paged_ || prefix.is_none(),
+                    "kv_layout paged does not support prefix (shared-prefix "
+                    "attention reads contiguous slots)");
+        const size_t layer_stride =
+            paged_ ? (size_t)pages_ * kv_page_rows() * EK_
+                   : (size_t)B_ * ctx_ * EK_;
         // q8: byte caches, addressed through k8/v8 below; the f16 kernels
         // see the single-layer stages
         __half* kbase = kv8_ ? nullptr
@@ -495,6 +546,14 @@ class SliceEngine {
                     hipGetErrorString(e));
         };
         float* slab = slab_.data_ptr<float>();
+        const int* tbl = nullptr;
+        int* kv_row = nullptr;
+        if (paged_) {  // the pool row of every new K/V row, for all layers
+            tbl = table_.data_ptr<int>();
+            kv_row = kv_row_.data_ptr<int>();
+            launch_paged_rows(s, tbl, pp, sp, kv_row, T, ctx_);
+            ck("paged rows", 0);
+        }
         const int route = attn_route(H_, HK_, T, decode ? 1 : 0,
                                      gqa_attention_ ? 1 : 0);
         for (int li = 0; li < L_; ++li) {
@@ -503,13 +562,14 @@ class SliceEngine {
                               : kbase + (size_t)li * layer_stride;
             __half* vc = kv8_ ? reinterpret_cast<__half*>(v_stage_.data_ptr())
                               : vbase + (size_t)li * layer_stride;
-            // the GQA and q8 kernels have no fused prologue: k_qkv_finish
-            // runs
+            // the GQA, q8 and paged kernels have no fused prologue:
+            // k_qkv_finish runs
             const int slab_used = launch_qkv16(
                 s, l.mq.w, l.mk.w, l.mv.w, xprep, ssa + li * ssw_, eps_,
                 qb, kc, vc, pp, sp, ifr, E_, EK_, D_, ctx_, T, slab,
                 /*skip_finish=*/
-                (decode && route != 2 && !shared && !kv8_) ? 1 : 0);
+                (decode && route != 2 && !shared && !kv8_ && !paged_) ? 1 : 0,
+                kv_row);
             ck("qkv", li);
             // 16-query tiles are spans for prefill; the distinct-sequence
             // decode shape streams per token at any T, fused with the
@@ -545,6 +605,11 @@ class SliceEngine {
                     launch_attn_kv8(s, qb, k8, v8, ksc, vsc, ab, aprep, pp,
                                     sp, T, H_, HK_, E_, EK_, D_, ctx_,
                                     kv8_ws_.data_ptr<float>());
+            } else if (paged_) {
+                // every T, prompt spans included, per token over the pools
+                launch_attn_paged(s, qb, kc, vc, tbl, ab, aprep, pp, sp, T,
+                                  H_, HK_, E_, EK_, D_, ctx_,
+                                  paged_ws_.data_ptr<float>());
             } else if (shared) {
                 launch_attn_prefix(s, qb, kc, vc, ab, aprep, pp, sp, fp,
                                    pslot, plen, T, H_, HK_, E_, EK_, D_,
@@ -782,6 +847,11 @@ class SliceEngine {
     torch::Tensor v_cache() const { return v_cache_; }
     torch::Tensor k_scale() const { return k_scale_; }
     torch::Tensor v_scale() const { return v_scale_; }
+    // kv_layout paged: k_cache / v_cache are the pools [L, kv_pages * 16,
+    // Ekv]; the block table i32 [B, ceil(ctx / 16)] is the caller's to fill
+    // (undefined on a contiguous engine)
+    torch::Tensor block_table() const { return table_; }
+    int64_t kv_pages() const { return pages_; }
 
  private:
     void forward_legacy(hipStream_t s, float* xp, const int* pp,
@@ -819,6 +889,8 @@ class SliceEngine {
     bool kv8_;               // kv_dtype q8: byte caches, k_attn_kv8
     bool kv8_prefill_;       // q8 prompt spans > 64: k_attn_kv8_prefill
     bool kv8_prefix_;        // q8 serves prefix: launch_attn_kv8_prefix
+    bool paged_;             // kv_layout paged: page pools, k_attn_paged
+    int64_t pages_;          // pages per layer pool (page 0 = scratch)
     std::vector<Layer> layers_;
     std::vector<bool> loaded_;
     torch::Tensor kv_store_k_, kv_store_v_;
@@ -830,6 +902,8 @@ class SliceEngine {
     // kv_dtype q8 only: scale planes, single-layer f16 stages, split-KV ws
     torch::Tensor k_scale_, v_scale_, k_stage_, v_stage_, kv8_ws_;
     torch::Tensor kv8_prefix_ws_;  // kv8_prefix: allocated by the constructor
+    // kv_layout paged only: block table, k_paged_rows' output, split-KV ws
+    torch::Tensor table_, kv_row_, paged_ws_;
     // prompt scoring, allocated by the first score() call
     torch::Tensor ss_score_, score_key_, score_sum_, score_tgt_;
     bool has_extra_ = false;
@@ -1121,6 +1195,73 @@ AttnResult attention_kv8_prefix(torch::Tensor q, torch::Tensor k8,
                            seq.data_ptr<int>(), pfx.data_ptr<int>(),
                            (int)pslot, (int)P, d.T, d.H, d.Hkv, d.E, d.Ekv,
                            d.D, d.ctx, ws.data_ptr<float>());
+    return r;
+}
+
+// The paged hooks' table: i32 [n_slots, ceil(n_ctx / 16)] on the device
+void check_block_table(const torch::Tensor& table, int64_t n_ctx) {
+    check_i32(table, "table");
+    TORCH_CHECK(n_ctx >= 1 && n_ctx <= kPagedMaxCtx, "n_ctx out of range");
+    TORCH_CHECK(table.dim() == 2 && table.size(0) >= 1 &&
+                    table.size(1) ==
+                        (n_ctx + kv_page_rows() - 1) / kv_page_rows(),
+                "table must be [n_slots, ceil(n_ctx / 16)]");
+}
+
+// k_paged_rows: the pool row of (seq[t], pos[t]) for every t -> i32 [T]
+torch::Tensor paged_rows(torch::Tensor table, torch::Tensor pos,
+                         torch::Tensor seq, int64_t n_ctx) {
+    check_block_table(table, n_ctx);
+    check_attn_dims(pos.numel(), 1, 1, 16, n_ctx, table.size(0), pos, seq);
+    auto rows = torch::empty_like(pos);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    launch_paged_rows(s, table.data_ptr<int>(), pos.data_ptr<int>(),
+                      seq.data_ptr<int>(), rows.data_ptr<int>(),
+                      (int)pos.numel(), (int)n_ctx);
+    return rows;
+}
+
+// k_attn_paged (+ k_attn_gqa_merge) over pools of f16 [pages * 16 * Ekv +
+// 16] (the pad is mandatory: the kernel reads whole 16-byte spans past the
+// last head); every table entry must name a page of the pools. The split-KV
+// workspace is per call.
+AttnResult attention_paged(torch::Tensor q, torch::Tensor k_pool,
+                           torch::Tensor v_pool, torch::Tensor table,
+                           torch::Tensor pos, torch::Tensor seq,
+                           int64_t n_head, int64_t n_head_kv,
+                           int64_t n_ctx) {
+    check_f32(q, "q");
+    TORCH_CHECK(q.dim() == 2 && q.size(0) >= 1, "q must be [T, E]");
+    TORCH_CHECK(n_head >= 1 && q.size(1) % n_head == 0,
+                "E not divisible by n_head");
+    check_block_table(table, n_ctx);
+    const AttnDims d = check_attn_dims(q.size(0), n_head, n_head_kv,
+                                       q.size(1) / n_head, n_ctx,
+                                       table.size(0), pos, seq);
+    TORCH_CHECK(d.H / d.Hkv <= 64, "paged serves n_head / n_head_kv <= 64");
+    const int64_t page_halves = (int64_t)kv_page_rows() * d.Ekv;
+    for (const torch::Tensor* t : {&k_pool, &v_pool})
+        TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->dim() == 1 &&
+                        t->scalar_type() == torch::kFloat16 &&
+                        t->numel() == k_pool.numel() && t->numel() > 16 &&
+                        (t->numel() - 16) % page_halves == 0,
+                    "k_pool/v_pool must be flat f16 device tensors of "
+                    "pages*16*Ekv + 16 halves");
+    const int64_t pages = (k_pool.numel() - 16) / page_halves;
+    TORCH_CHECK(pages * kv_page_rows() <= INT32_MAX, "too many pages");
+    TORCH_CHECK(table.min().item<int64_t>() >= 0 &&
+                    table.max().item<int64_t>() < pages,
+                "table entry out of [0, pages)");
+    AttnResult r = alloc_attn_result(d);
+    auto ws = torch::zeros(
+        {paged_ws_numel(d.H, d.D, d.ctx)},
+        torch::TensorOptions().device(torch::kCUDA).dtype(torch::kFloat32));
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    launch_attn_paged(s, q.data_ptr<float>(), h16c(k_pool), h16c(v_pool),
+                      table.data_ptr<int>(),
+                      std::get<0>(r).data_ptr<float>(), u16p(std::get<1>(r)),
+                      pos.data_ptr<int>(), seq.data_ptr<int>(), d.T, d.H,
+                      d.Hkv, d.E, d.Ekv, d.D, d.ctx, ws.data_ptr<float>());
     return r;
 }
 
@@ -1543,6 +1684,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("attn_kv8_prefix_splits", [](int64_t n_ctx, int64_t T) {
         return (int64_t)attn_kv8_prefix_splits((int)n_ctx, (int)T);
     }, py::arg("n_ctx"), py::arg("T"));
+    m.def("paged_rows", &paged_rows, py::arg("table"), py::arg("pos"),
+          py::arg("seq"), py::arg("n_ctx"));
+    m.def("attention_paged", &attention_paged, py::arg("q"),
+          py::arg("k_pool"), py::arg("v_pool"), py::arg("table"),
+          py::arg("pos"), py::arg("seq"), py::arg("n_head"),
+          py::arg("n_head_kv"), py::arg("n_ctx"));
+    m.def("attn_paged_chunk", [](int64_t n_ctx) {
+        return (int64_t)attn_paged_chunk((int)n_ctx);
+    }, py::arg("n_ctx"));
+    m.def("attn_paged_splits", [](int64_t n_ctx, int64_t T) {
+        return (int64_t)attn_paged_splits((int)n_ctx, (int)T);
+    }, py::arg("n_ctx"), py::arg("T"));
+    m.def("kv_page_rows", []() { return (int64_t)kv_page_rows(); });
     m.def("attn_prefix_chunk", [](int64_t n_ctx) {
         return (int64_t)attn_prefix_chunk((int)n_ctx);
     }, py::arg("n_ctx"));
@@ -1582,13 +1736,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     py::class_<SliceEngine, std::shared_ptr<SliceEngine>>(m, "SliceEngine")
         .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                       double, double, int64_t, int64_t, bool, int64_t,
-                      bool, bool>(),
+                      bool, bool, int64_t, int64_t>(),
              py::arg("n_embd"), py::arg("n_head"), py::arg("n_layers"),
              py::arg("n_ff"), py::arg("n_ctx"), py::arg("max_batch"),
              py::arg("eps"), py::arg("rope_base"),
              py::arg("max_prefill") = 1024, py::arg("n_head_kv") = 0,
              py::arg("gqa_attention") = true, py::arg("kv_dtype") = 0,
-             py::arg("kv8_prefill") = true, py::arg("kv8_prefix") = false)
+             py::arg("kv8_prefill") = true, py::arg("kv8_prefix") = false,
+             py::arg("kv_layout") = 0, py::arg("kv_pages") = 0)
         .def("set_layer", &SliceEngine::set_layer)
         .def("set_extra", &SliceEngine::set_extra)
         .def("forward", &SliceEngine::forward, py::arg("x"),
@@ -1613,5 +1768,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         .def_property_readonly("k_cache", &SliceEngine::k_cache)
         .def_property_readonly("v_cache", &SliceEngine::v_cache)
         .def_property_readonly("k_scale", &SliceEngine::k_scale)
-        .def_property_readonly("v_scale", &SliceEngine::v_scale);
+        .def_property_readonly("v_scale", &SliceEngine::v_scale)
+        .def_property_readonly("block_table", &SliceEngine::block_table)
+        .def_property_readonly("kv_pages", &SliceEngine::kv_pages);
 }

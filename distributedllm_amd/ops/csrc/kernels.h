@@ -85,14 +85,18 @@ void launch_prep_x(hipStream_t s, const float* x, unsigned short* xprep,
 // T <= 64: slab != nullptr enables the RT=2 + split-K slab path for small
 // models; returns 1 when the slab path ran. skip_finish=1 leaves the slabs
 // un-combined for a fused-attention consumer (decode only). T > 64 ignores
-// slab and skip_finish and returns 0.
+// slab and skip_finish and returns 0. kv_row = nullptr: token t's K/V row is
+// row seq[t] * n_ctx + pos[t] of the layer's caches. Otherwise it is row
+// kv_row[t] (device i32 [T], the paged layout's launch_paged_rows); the
+// fused-attention consumer knows no kv_row, so skip_finish must be 0 then.
 int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
                  const WMat2& wv, const unsigned short* xprep,
                  const float* ss_in, float eps, float* q_buf,
                  __half* k_cache_layer,
                  __half* v_cache_layer, const int* pos, const int* seq,
                  const float* inv_freq, int E, int Ekv, int D, int n_ctx,
-                 int T, float* slab, int skip_finish);
+                 int T, float* slab, int skip_finish,
+                 const int* kv_row = nullptr);
 
 void launch_ffn16(hipStream_t s, const WMat2& w1, const WMat2& w3,
                   const unsigned short* xprep, const float* ss_in,
@@ -241,6 +245,42 @@ void launch_attn_kv8_prefix(hipStream_t s, const float* q_buf,
                             const int* seq, const int* pfx, int pslot, int P,
                             int T, int H, int Hkv, int E, int Ekv, int D,
                             int n_ctx, float* ws);
+
+// ------------------------------------------------ paged KV cache
+// attention_paged.hip. A page is kv_page_rows() = 16 rows of Ekv halves (one
+// MFMA row tile). K and V pools: f16 [kv_pages * 16, Ekv] per layer (+ 16
+// halves of tail pad on the whole allocation). table: device i32
+// [slots, ceil(n_ctx / 16)], shared by all layers; row r of slot s is pool
+// row table[s][r / 16] * 16 + r % 16. Every entry is a page id in
+// [0, kv_pages): page 0 is never assigned and stands for "no page" (written
+// and read like any other, its rows only ever masked).
+//   launch_paged_rows  k_paged_rows: kv_row[t] = pool row of (seq[t],
+//                      pos[t]), the `kv_row` argument of launch_qkv16
+//   launch_attn_paged  k_attn_paged (+ k_attn_gqa_merge): launch_attn_kv8's
+//                      contract over the f16 pools: every 1 <= H/Hkv <= 64
+//                      and every T, one block per (token, KV head, 16 query
+//                      heads, KV chunk) on the matrix cores. Token t attends
+//                      rows [0, pos[t]] of slot seq[t] through the table.
+//                      Splits follow the GQA rule (functions of n_ctx alone
+//                      for T <= 64, one split for T > 64): a token's bits do
+//                      not depend on T, on the other tokens or on which
+//                      pages hold its rows. ws: f32 [64][H][S][D + 2] with
+//                      S = attn_paged_splits(n_ctx, 1); untouched when S = 1.
+//                      Dynamic LDS holds ceil(chunk / 16) page ids: callers
+//                      keep n_ctx <= 65536.
+int kv_page_rows();
+int attn_paged_chunk(int n_ctx);
+int attn_paged_splits(int n_ctx, int T);
+
+void launch_paged_rows(hipStream_t s, const int* table, const int* pos,
+                       const int* seq, int* kv_row, int T, int n_ctx);
+
+void launch_attn_paged(hipStream_t s, const float* q_buf,
+                       const __half* k_pool_layer,
+                       const __half* v_pool_layer, const int* table,
+                       float* out, unsigned short* out_prep, const int* pos,
+                       const int* seq, int T, int H, int Hkv, int E, int Ekv,
+                       int D, int n_ctx, float* ws);
 
 // ------------------------------------------------ shared-prefix attention
 // Token t attends rows [0, pfx[t]) of slot `pslot`, then rows

@@ -829,6 +829,16 @@ __global__ __launch_bounds__(BLOCK) void k_qkv16_slab(
     }
 }
 
+// The cache row that token t's K/V row is written to: contiguous slots
+// (kv_row = nullptr: slot seq[t], row p = pos[t]) or row-indirect (the paged
+// layout: kv_row[t], filled by k_paged_rows).
+__device__ __forceinline__ size_t kv_row_of(const int* __restrict__ kv_row,
+                                            const int* __restrict__ seq,
+                                            int t, int n_ctx, int p) {
+    return kv_row != nullptr ? (size_t)kv_row[t]
+                             : (size_t)seq[t] * n_ctx + p;
+}
+
 // Sum the qkv slabs, apply RoPE, write q_buf / KV caches. One thread per
 // (mat, 8-row chunk, token): vectorized float4 slab reads and uint4/f16x8
 // stores (scalar 2-4 B accesses made the first version a 5 us kernel).
@@ -839,7 +849,8 @@ __global__ void k_qkv_finish(const float* __restrict__ slab, int ks,
                              const int* __restrict__ pos,
                              const int* __restrict__ seq,
                              const float* __restrict__ inv_freq, int E,
-                             int Ekv, int D, int n_ctx, int T) {
+                             int Ekv, int D, int n_ctx, int T,
+                             const int* __restrict__ kv_row) {
     const int nchunks = (E + 2 * Ekv) / 8;
     const int idx = blockIdx.x * BLOCK + threadIdx.x;
     if (idx >= nchunks * T) return;
@@ -861,7 +872,7 @@ __global__ void k_qkv_finish(const float* __restrict__ slab, int ks,
     }
     const int p = pos[t];
     if (mat == 2) {
-        __half* dst = v_cache + ((size_t)seq[t] * n_ctx + p) * Ekv + e;
+        __half* dst = v_cache + kv_row_of(kv_row, seq, t, n_ctx, p) * Ekv + e;
         uint4 o;
         o.x = pack_f16(v[0], v[1]);
         o.y = pack_f16(v[2], v[3]);
@@ -887,7 +898,7 @@ __global__ void k_qkv_finish(const float* __restrict__ slab, int ks,
         *reinterpret_cast<float4*>(dst + 4) =
             make_float4(o[4], o[5], o[6], o[7]);
     } else {
-        __half* dst = k_cache + ((size_t)seq[t] * n_ctx + p) * Ekv + e;
+        __half* dst = k_cache + kv_row_of(kv_row, seq, t, n_ctx, p) * Ekv + e;
         uint4 w;
         w.x = pack_f16(o[0], o[1]);
         w.y = pack_f16(o[2], o[3]);
@@ -944,7 +955,7 @@ __global__ __launch_bounds__(BLOCK) void k_qkv16(
     __half* __restrict__ k_cache, __half* __restrict__ v_cache,
     const int* __restrict__ pos, const int* __restrict__ seq,
     const float* __restrict__ inv_freq, int E, int Ekv, int D, int n_ctx,
-    int T, int MT, int jtw_rt) {
+    int T, int MT, int jtw_rt, const int* __restrict__ kv_row) {
     int gtile, mtile, jtw;
     const int tq = (E >> 4) / RT;
     const int tk = (Ekv >> 4) / RT;
@@ -984,7 +995,7 @@ __global__ __launch_bounds__(BLOCK) void k_qkv16(
         const int p = pos[j2];
         if (mat == 2) {  // V rows: straight f16 cache append
             __half* dst =
-                v_cache + ((size_t)seq[j2] * n_ctx + p) * Ekv + r0;
+                v_cache + kv_row_of(kv_row, seq, j2, n_ctx, p) * Ekv + r0;
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj)
                 dst[jj] = __float2half(acc[rt][0][jt][jj]);
@@ -1006,7 +1017,8 @@ __global__ __launch_bounds__(BLOCK) void k_qkv16(
                 q_buf[(size_t)j2 * E + e + 1] = o1;
             } else {
                 __half* dst =
-                    k_cache + ((size_t)seq[j2] * n_ctx + p) * Ekv + e;
+                    k_cache + kv_row_of(kv_row, seq, j2, n_ctx, p) * Ekv +
+                    e;
                 dst[0] = __float2half(o0);
                 dst[1] = __float2half(o1);
             }
@@ -1417,7 +1429,7 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
                  __half* k_cache_layer,
                  __half* v_cache_layer, const int* pos, const int* seq,
                  const float* inv_freq, int E, int Ekv, int D, int n_ctx,
-                 int T, float* slab, int skip_finish) {
+                 int T, float* slab, int skip_finish, const int* kv_row) {
     const int tiles3 = (E + 2 * Ekv) >> 4;
     if (T > 64) {
         const int MT = (T + 63) >> 6;
@@ -1428,7 +1440,7 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
                 dim3(xcd_grid(tiles3 / RTc, MT)), dim3(BLOCK), 0, s, wq, wk,
                 wv, xprep, ss_in, eps, q_buf, k_cache_layer,
                 v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T, MT,
-                jtw)));
+                jtw, kv_row)));
         return 0;
     }
     const int route = qkv16_route(E, Ekv, T, slab != nullptr);
@@ -1445,7 +1457,7 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
                                dim3((total + BLOCK - 1) / BLOCK),
                                dim3(BLOCK), 0, s, slab, ks, q_buf,
                                k_cache_layer, v_cache_layer, pos, seq,
-                               inv_freq, E, Ekv, D, n_ctx, T);
+                               inv_freq, E, Ekv, D, n_ctx, T, kv_row);
         }
         return 1;
     }
@@ -1454,7 +1466,8 @@ int launch_qkv16(hipStream_t s, const WMat2& wq, const WMat2& wk,
         hipLaunchKernelGGL(
             (k_qkv16<WTc, JTc, RTc>), dim3(tiles3 / RTc), dim3(BLOCK), 0, s,
             wq, wk, wv, xprep, ss_in, eps, q_buf, k_cache_layer,
-            v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T, 0, 0))));
+            v_cache_layer, pos, seq, inv_freq, E, Ekv, D, n_ctx, T, 0, 0,
+            kv_row))));
     return 0;
 }
 

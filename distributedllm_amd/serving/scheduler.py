@@ -127,7 +127,15 @@ class ContinuousBatcher:
         whose forward takes no `prefix` (the pipeline facade), a prefix
         that does not fit n_ctx or the engine's max_prefill (its
         `prefill_cap`), or when no
-        slot would be left for requests."""
+        slot would be left for requests.
+
+        Engines with kv_layout="paged": admission also reserves, in the
+        slot's lane, the pages of every row the request can ever write,
+        len(prompt) + max_new rows (a speculative draft is capped at
+        max_new - len(out) - 1 tokens, `_draft`, so no row lies past that).
+        The request at the head of the queue waits until a free slot's lane
+        has the pages; finish and cancel give them back. n_slots stays
+        bounded by max_batch. shared_prefix is refused."""
         self.engine = engine
         self.lanes = engines if engines else [engine]
         k = len(self.lanes)
@@ -136,6 +144,12 @@ class ContinuousBatcher:
         slots = per_lane * k
         if max_slots is not None:
             slots = min(slots, max_slots)
+        self._paged = any(getattr(e, "kv_layout", "contiguous") == "paged"
+                          for e in self.lanes)
+        if self._paged and shared_prefix is not None:
+            raise ValueError("shared_prefix and kv_layout='paged' cannot be "
+                             "combined: shared-prefix attention reads "
+                             "contiguous slots")
         self._prefix: List[int] = list(map(int, shared_prefix or []))
         self._prefix_slot = per_lane - 1    # lane-local
         self._prefix_ready = False
@@ -195,6 +209,38 @@ class ContinuousBatcher:
         k = len(self.lanes)
         return self.lanes[slot % k], slot // k
 
+    def _lane_ctx(self, slot: int):
+        """The stream of `slot`'s lane: table updates must order with that
+        lane's forwards."""
+        if self._streams is None:
+            return _nullctx()
+        return torch.cuda.stream(self._streams[slot % len(self.lanes)])
+
+    def _kv_take(self, r: Request) -> int:
+        """A free slot for `r`, its KV pages reserved on a paged engine:
+        removed from `free` and returned, or -1 when no free slot's lane has
+        the pages."""
+        if not self._paged:
+            return self.free.pop()
+        n_ctx = getattr(self.engine, "n_ctx", 1 << 30)
+        rows = min(len(r.prompt) + r.max_new, n_ctx)
+        for slot in reversed(self.free):
+            eng, local = self._lane(slot)
+            with self._lane_ctx(slot):
+                ok = eng.kv_reserve(local, rows)
+            if ok:
+                self.free.remove(slot)
+                return slot
+        return -1
+
+    def _release(self, slot: int) -> None:
+        """`slot` back to the free list, its pages to its lane's pool."""
+        if self._paged:
+            eng, local = self._lane(slot)
+            with self._lane_ctx(slot):
+                eng.kv_release(local)
+        self.free.append(slot)
+
     # ------------------------------------------------------------- intake
 
     def submit(self, prompt_ids: Sequence[int], max_new: int,
@@ -242,6 +288,13 @@ class ContinuousBatcher:
             raise ValueError(
                 f"prompt ({len(prompt_ids)}) + max_new ({max_new}) "
                 f"exceeds n_ctx={n_ctx}")
+        if self._paged:
+            need = self.engine.kv_pages_for(len(prompt_ids) + max_new)
+            pool = min(e.kv_pages for e in self.lanes) - 1
+            if need > pool:
+                raise ValueError(
+                    f"prompt ({len(prompt_ids)}) + max_new ({max_new}) needs "
+                    f"{need} KV pages, the pool holds {pool}")
         r = Request(rid=self._next_rid, prompt=list(map(int, prompt_ids)),
                     max_new=max_new, sampler=sampler,
                     eos_id=self.eos_id if eos_id is None else eos_id,
@@ -290,14 +343,19 @@ class ContinuousBatcher:
         # take queued requests into free slots; their prompt body
         # prefills below (possibly across several steps when chunked)
         while self.free and self.queue:
-            r = self.queue.popleft()
+            r = self.queue[0]
             # submit() already validated against n_ctx; this is a cheap
             # backstop against an engine swap shrinking n_ctx after
             # submission — drop the request rather than corrupt the KV
             if len(r.prompt) + r.max_new > n_ctx:
+                self.queue.popleft()
                 r.done = True
                 continue
-            r.slot = self.free.pop()
+            slot = self._kv_take(r)
+            if slot < 0:    # paged: the head waits for pages to free up
+                break
+            self.queue.popleft()
+            r.slot = slot
             shares = (P > 0 and len(r.prompt) > P and not r.echo and
                       r.prompt[:P] == self._prefix)
             r._pfx = P if shares else 0
@@ -369,7 +427,7 @@ class ContinuousBatcher:
             self._activate(r)
             return
         r.done = True
-        self.free.append(r.slot)
+        self._release(r.slot)
         r.slot = -1
         finished.append(r)
 
@@ -659,7 +717,7 @@ class ContinuousBatcher:
                                                tid == r.eos_id):
                     r.done = True
                     del self.active[r.slot]
-                    self.free.append(r.slot)
+                    self._release(r.slot)
                     r.slot = -1
                     finished.append(r)
                     break
@@ -674,7 +732,7 @@ class ContinuousBatcher:
                               req.slot in self.prefilling):
             self.active.pop(req.slot, None)
             self.prefilling.pop(req.slot, None)
-            self.free.append(req.slot)
+            self._release(req.slot)
             req.slot = -1
         else:
             try:
