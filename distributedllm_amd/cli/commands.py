@@ -342,6 +342,8 @@ class BatchGenerateCommand(Command):
         from ..formats import ggml, slicer
         from ..serving import ContinuousBatcher
 
+        if _paged_prefill_misuse(args):
+            return 2
         prompts = list(args.prompt or [])
         if args.prompts_file:
             with open(args.prompts_file) as f:
@@ -360,7 +362,8 @@ class BatchGenerateCommand(Command):
                                kv_dtype=args.kv_dtype,
                                kv8_prefix=_wants_kv8_prefix(args),
                                kv_layout=args.kv_layout,
-                               kv_pages=args.kv_pages)
+                               kv_pages=args.kv_pages,
+                               paged_prefill=args.paged_prefill)
         eng.attach_extra(slicer.make_extra_layers(f))
         tok = Tokenizer(f.vocab)
         prefix = _read_shared_prefix(args.shared_prefix_file, tok)
@@ -436,6 +439,19 @@ def _add_kv_layout_args(p: argparse.ArgumentParser) -> None:
                    help="pages in the pool of a paged KV cache, per lane "
                         "(default: slots * ceil(ctx / 16) + 1, the "
                         "contiguous capacity)")
+    p.add_argument("--paged-prefill", action="store_true",
+                   help="with --kv-layout paged: prompt spans of more than "
+                        "64 tokens run the Q-tiled attention kernel (a K/V "
+                        "row is read once per 16 prompt tokens, not once "
+                        "per token)")
+
+
+def _paged_prefill_misuse(args) -> bool:
+    """--paged-prefill without --kv-layout paged: say so, caller returns 2."""
+    if args.paged_prefill and args.kv_layout != "paged":
+        print("--paged-prefill needs --kv-layout paged", file=sys.stderr)
+        return True
+    return False
 
 
 def _wants_kv8_prefix(args) -> bool:
@@ -512,6 +528,8 @@ class ServeHttpCommand(Command):
         from ..formats import ggml, slicer
         from ..serving import ContinuousBatcher, build_http_app
 
+        if _paged_prefill_misuse(args):
+            return 2
         if args.pipeline:
             if args.shared_prefix_file:
                 print("--shared-prefix-file is single-engine only",
@@ -533,7 +551,8 @@ class ServeHttpCommand(Command):
                                kv_dtype=args.kv_dtype,
                                kv8_prefix=_wants_kv8_prefix(args),
                                kv_layout=args.kv_layout,
-                               kv_pages=args.kv_pages)
+                               kv_pages=args.kv_pages,
+                               paged_prefill=args.paged_prefill)
         eng.attach_extra(slicer.make_extra_layers(f))
         lanes = None
         if n_lanes > 1 and hasattr(eng, "clone_shared"):

@@ -48,6 +48,12 @@ def _check_kv_layout(kv_layout: str) -> str:
     return kv_layout
 
 
+def _check_paged_prefill(paged_prefill: bool, kv_layout: str) -> bool:
+    if paged_prefill and kv_layout != "paged":
+        raise ValueError("paged_prefill needs kv_layout='paged'")
+    return bool(paged_prefill)
+
+
 def quantize_kv_rows(x: torch.Tensor) -> torch.Tensor:
     """Fake-quantise K/V rows the way the q8 cache stores them (ops/csrc/
     attention_kv8.hip), in f32: per head (last axis) s = f16(amax / 127),
@@ -70,7 +76,8 @@ class HIPSliceEngine:
                  gqa_attention: bool = True, kv_dtype: str = "f16",
                  kv8_prefill: bool = True, kv8_prefix: bool = False,
                  kv_layout: str = "contiguous",
-                 kv_pages: Optional[int] = None):
+                 kv_pages: Optional[int] = None,
+                 paged_prefill: bool = False):
         from .. import ops
         core = ops.core()
         self.hp = hp
@@ -97,6 +104,9 @@ class HIPSliceEngine:
         # The default pool has today's capacity (+ the scratch page 0).
         self.kv_layout = _check_kv_layout(kv_layout)
         paged = kv_layout == "paged"
+        # paged prompt spans of more than 64 tokens in one call: the Q-tiled
+        # k_attn_paged_prefill; False keeps k_attn_paged at every T
+        self.paged_prefill = _check_paged_prefill(paged_prefill, kv_layout)
         if paged and self.kv_dtype != "f16":
             raise ValueError("kv_layout='paged' and kv_dtype='q8' cannot be "
                              "combined: the page pools are f16")
@@ -125,7 +135,7 @@ class HIPSliceEngine:
             gqa_attention=gqa_attention,
             kv_dtype=KV_DTYPES.index(kv_dtype), kv8_prefill=kv8_prefill,
             kv8_prefix=kv8_prefix, kv_layout=KV_LAYOUTS.index(kv_layout),
-            kv_pages=self.kv_pages)
+            kv_pages=self.kv_pages, paged_prefill=self.paged_prefill)
         self.device = "cuda"
         self.has_extra = False
         # weight-tensor references for clone_shared (filled by .random()
@@ -139,13 +149,15 @@ class HIPSliceEngine:
                   max_batch: int = 16, gqa_attention: bool = True,
                   kv_dtype: str = "f16", kv8_prefill: bool = True,
                   kv8_prefix: bool = False, kv_layout: str = "contiguous",
-                  kv_pages: Optional[int] = None) -> "HIPSliceEngine":
+                  kv_pages: Optional[int] = None,
+                  paged_prefill: bool = False) -> "HIPSliceEngine":
         hp = f.hparams
         first = hp.first_layer if hp.first_layer is not None else 0
         eng = cls(hp, hp.n_layer, first, n_ctx, max_batch,
                   gqa_attention=gqa_attention, kv_dtype=kv_dtype,
                   kv8_prefill=kv8_prefill, kv8_prefix=kv8_prefix,
-                  kv_layout=kv_layout, kv_pages=kv_pages)
+                  kv_layout=kv_layout, kv_pages=kv_pages,
+                  paged_prefill=paged_prefill)
         eng.load_layers(f)
         return eng
 
@@ -157,7 +169,8 @@ class HIPSliceEngine:
                gqa_attention: bool = True, kv_dtype: str = "f16",
                kv8_prefill: bool = True, kv8_prefix: bool = False,
                kv_layout: str = "contiguous",
-               kv_pages: Optional[int] = None) -> "HIPSliceEngine":
+               kv_pages: Optional[int] = None,
+               paged_prefill: bool = False) -> "HIPSliceEngine":
         """Random-init engine straight on the GPU (synthetic benchmarking).
 
         Generates weights directly in the repacked kernel layout — identical
@@ -168,7 +181,7 @@ class HIPSliceEngine:
                   max_prefill=max_prefill, gqa_attention=gqa_attention,
                   kv_dtype=kv_dtype, kv8_prefill=kv8_prefill,
                   kv8_prefix=kv8_prefix, kv_layout=kv_layout,
-                  kv_pages=kv_pages)
+                  kv_pages=kv_pages, paged_prefill=paged_prefill)
         g = torch.Generator(device="cuda")
         g.manual_seed(seed)
         E, F, V = hp.n_embd, hp.n_ff, hp.n_vocab
@@ -241,7 +254,8 @@ class HIPSliceEngine:
                               kv8_prefill=self.kv8_prefill,
                               kv8_prefix=self.kv8_prefix,
                               kv_layout=self.kv_layout,
-                              kv_pages=self.kv_pages or None)
+                              kv_pages=self.kv_pages or None,
+                              paged_prefill=self.paged_prefill)
         for li, (an, fn, mats) in enumerate(self._layers_cache):
             twin._eng.set_layer(li, an, fn, mats)
         twin._layers_cache = self._layers_cache  # enables further clones
@@ -562,8 +576,12 @@ class TorchSliceEngine:
     @classmethod
     def from_ggml(cls, f: ggml.GGMLFile, n_ctx: int = 512,
                   max_batch: int = 4, kv_dtype: str = "f16",
-                  kv8_prefix: bool = False) -> "TorchSliceEngine":
+                  kv8_prefix: bool = False, kv_layout: str = "contiguous",
+                  paged_prefill: bool = False) -> "TorchSliceEngine":
+        """kv_layout and paged_prefill change no result: they are checked as
+        HIPSliceEngine checks them and otherwise ignored."""
         from ..models.llama import weights_from_ggml
+        _check_paged_prefill(paged_prefill, _check_kv_layout(kv_layout))
         hp = f.hparams
         first = hp.first_layer if hp.first_layer is not None else 0
         return cls(hp, weights_from_ggml(f), hp.n_layer, first, n_ctx,
@@ -730,11 +748,12 @@ def engine_for_slice(f: ggml.GGMLFile, n_ctx: int, max_batch: int,
                      device: Optional[str] = None, kv_dtype: str = "f16",
                      kv8_prefix: bool = False,
                      kv_layout: str = "contiguous",
-                     kv_pages: Optional[int] = None):
+                     kv_pages: Optional[int] = None,
+                     paged_prefill: bool = False):
     """Pick the engine for this machine: HIP when a GPU is present. The KV
-    layout changes no result, so the CPU twin has none: kv_layout and
-    kv_pages are checked and otherwise ignored there."""
-    _check_kv_layout(kv_layout)
+    layout changes no result, so the CPU twin has none: kv_layout, kv_pages
+    and paged_prefill are checked and otherwise ignored there."""
+    _check_paged_prefill(paged_prefill, _check_kv_layout(kv_layout))
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     if device == "cuda":
@@ -742,7 +761,8 @@ def engine_for_slice(f: ggml.GGMLFile, n_ctx: int, max_batch: int,
                                         kv_dtype=kv_dtype,
                                         kv8_prefix=kv8_prefix,
                                         kv_layout=kv_layout,
-                                        kv_pages=kv_pages)
+                                        kv_pages=kv_pages,
+                                        paged_prefill=paged_prefill)
     return TorchSliceEngine.from_ggml(f, n_ctx=n_ctx, max_batch=max_batch,
                                       kv_dtype=kv_dtype,
                                       kv8_prefix=kv8_prefix)

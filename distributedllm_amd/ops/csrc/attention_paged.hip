@@ -1,7 +1,7 @@
 // Paged KV cache (kv_layout = paged, gfx950): `k_paged_rows`, which turns
 // (block table, pos, seq) into the pool row every new K/V row is written to,
-// and `k_attn_paged` (+ k_attn_gqa_merge), decode-shaped attention over the
-// page pools. This file is compiled wholly without packed-f32 VALU
+// `k_attn_paged` (+ k_attn_gqa_merge), decode-shaped attention over the page
+// pools, and its Q-tiled prefill sibling `k_attn_paged_prefill`. This file is compiled wholly without packed-f32 VALU
 // instructions (NO_PACKED_F32 in ops/build.py).
 //
 // Layout. A page is PAGE_ROWS = 16 rows of Ekv halves, one MFMA row tile, so
@@ -260,6 +260,194 @@ __global__ __launch_bounds__(BLOCK) void k_attn_paged(
     }
 }
 
+// ----------------------------------------------------- prefill attention
+// k_attn_paged_prefill: k_attn_paged with the consumers of a KV row changed,
+// the step k_attn_kv8_prefill made from k_attn_kv8. One block per (16-query
+// tile, query head), grid (ceil(T/16), H): the 16 MFMA columns are the
+// tile's 16 queries for one head, so a K/V row is read once per 16 queries,
+// not once per query. No split-KV, no workspace: prefill launches are wide.
+// The tile's same-seq segments are walked as in k_attn_prefill_mfma. For a
+// segment with slot s and J = jmax + 1 the block copies the ceil(J / 16)
+// page ids of table row s into LDS (the segment loop is block-uniform, so
+// the copy sits between two block barriers and the tile loop has none), then
+// streams rows [0, J) with k_attn_paged's loop (paged_tile_page,
+// paged_load_tile, GqaTile as they are, cs = 0, ce = J). Score slot (row j,
+// column c) is live iff j < lim[c], lim = pos + 1 for a column of the
+// segment and 0 for any other: gqa_tile_step_q (attn_common.h), which also
+// holds the dead-column rules. Columns past T read no pos, seq or table
+// entry. Row 0 is attended by every token and belongs to wave 0's first
+// tile, so the merge sees l > 0 for every t < T.
+
+int attn_paged_route(int T, int decode, int paged_prefill) {
+    return (T > 64 && !decode && paged_prefill) ? 1 : 0;
+}
+
+// Dynamic LDS: one table row of page ids, ceil(n_ctx / 16) ints.
+template <int DC>
+__global__ __launch_bounds__(BLOCK) void k_attn_paged_prefill(
+    const float* __restrict__ q_buf, const __half* __restrict__ k_pool,
+    const __half* __restrict__ v_pool, const int* __restrict__ table,
+    float* __restrict__ out, unsigned short* __restrict__ out_prep,
+    const int* __restrict__ pos, const int* __restrict__ seq, int T, int grp,
+    int E, int Ekv, int D, int npg, int jtw) {
+    constexpr int NKC = DC > 1 ? DC / 2 : 1;
+    constexpr int QW = NKC * 32;        // staged q row, halves
+    const int t0 = (int)blockIdx.x * 16;
+    const int h = blockIdx.y;
+    const int hk = h / grp;             // GQA kv head
+    const int nq = min(16, T - t0);
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = __builtin_amdgcn_readfirstlane(tid / WAVE);  // scalar
+    const int lq = lane & 15;
+    const int lg = lane >> 4;
+    const float inv_sqrt_d = rsqrtf((float)D);
+    const __half* kb = k_pool + (size_t)hk * D;
+    const __half* vb = v_pool + (size_t)hk * D;
+
+    // LDS as in k_attn_paged: V tiles + staged Q while streaming, the waves'
+    // O partials [w][col][OSTR] after it, and the segment's page ids
+    constexpr int OSTR = DC * 16 + 4;
+    constexpr int VT_BYTES = NWAVES * 4 * GQA_VSTRIDE * (int)sizeof(uint2);
+    constexpr int Q_BYTES = 16 * (QW + 8) * (int)sizeof(_Float16);
+    constexpr int O_BYTES = NWAVES * 16 * OSTR * (int)sizeof(float);
+    constexpr int LDS_BYTES =
+        VT_BYTES + Q_BYTES > O_BYTES ? VT_BYTES + Q_BYTES : O_BYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
+    __shared__ float lds_m[NWAVES][16];
+    __shared__ float lds_l[NWAVES][16];
+    __shared__ int lds_pos[16];
+    __shared__ int lds_seq[16];         // -1 past T
+    extern __shared__ int lds_pg[];     // [npg]
+    uint2* vt = reinterpret_cast<uint2*>(lds_raw) + wid * 4 * GQA_VSTRIDE;
+    _Float16 (*lds_q)[QW + 8] =
+        reinterpret_cast<_Float16 (*)[QW + 8]>(lds_raw + VT_BYTES);
+    float* lds_o = reinterpret_cast<float*>(lds_raw);
+
+    if (tid < 16) {
+        const bool ok = tid < nq;
+        lds_pos[tid] = ok ? pos[t0 + (ok ? tid : 0)] : 0;
+        lds_seq[tid] = ok ? seq[t0 + (ok ? tid : 0)] : -1;
+    }
+    // Q tile -> LDS as f16, prescaled by 1/sqrt(D), zero past D and past T
+    // (the factor does the masking)
+    {
+        const float* qt = q_buf + (size_t)t0 * E + (size_t)h * D;
+#pragma unroll
+        for (int i = 0; i < 16 * QW / BLOCK; ++i) {
+            const int idx = tid + i * BLOCK;
+            const int col = idx / QW;
+            const int d = idx % QW;
+            const bool ok = col < nq && d < D;
+            const float v = qt[ok ? (size_t)col * E + d : 0] *
+                            (ok ? inv_sqrt_d : 0.0f);
+            lds_q[col][d] = (_Float16)v;
+        }
+    }
+    gqa_block_sync();
+    // score-MFMA B fragments: lane (column lq, k-span lg*8 of 32-d chunk c)
+    ABFrag qf[NKC];
+#pragma unroll
+    for (int c = 0; c < NKC; ++c) {
+        const uint4 u =
+            *reinterpret_cast<const uint4*>(&lds_q[lq][c * 32 + lg * 8]);
+        qf[c].u[0] = u.x; qf[c].u[1] = u.y;
+        qf[c].u[2] = u.z; qf[c].u[3] = u.w;
+    }
+    const int pos_q = lds_pos[lq];
+
+    float m = -INFINITY, l = 0.0f;      // running state of column lq
+    f32x4 oacc[DC];
+#pragma unroll
+    for (int dc = 0; dc < DC; ++dc) oacc[dc] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    constexpr int STEP = NWAVES * PAGE_ROWS;
+    int a = 0;
+    while (a < nq) {                    // same-seq segments, block-uniform
+        const int sseq = __builtin_amdgcn_readfirstlane(lds_seq[a]);
+        int b = a + 1;
+        while (b < nq && __builtin_amdgcn_readfirstlane(lds_seq[b]) == sseq)
+            ++b;
+        int jmax = 0;
+        for (int c = a; c < b; ++c)
+            jmax = max(jmax, __builtin_amdgcn_readfirstlane(lds_pos[c]));
+        const int J = jmax + 1;         // rows streamed: [0, J) of slot sseq
+        const int lim = (lq >= a && lq < b) ? pos_q + 1 : 0;
+        // the segment's page ids: entries 0 .. (J - 1)/16 of the slot's
+        // table row. The barrier that ended the previous segment (or the Q
+        // staging) lets them be overwritten.
+        {
+            const int* trow = table + (size_t)sseq * npg;
+            const int n = (J + PAGE_ROWS - 1) >> 4;
+            for (int i = tid; i < n; i += BLOCK) lds_pg[i] = trow[i];
+        }
+        gqa_block_sync();
+        // k_attn_paged's loop: wave w streams tiles w, w+4, ..., two per
+        // iteration in two buffers, loads one tile ahead, a tile's page id in
+        // a register before the loads of the tile in front of it are issued;
+        // rows at or past J read the slot's row 0 and are above every lim
+        int tj = wid * PAGE_ROWS;
+        if (tj < J) {                   // wave-uniform, scalar
+            const int pg0 = __builtin_amdgcn_readfirstlane(lds_pg[0]);
+            GqaTile<NKC> cur, alt;
+            int pn = paged_tile_page(lds_pg, tj + STEP, 0, J);
+            paged_load_tile(cur, kb, vb, paged_tile_page(lds_pg, tj, 0, J),
+                            pg0, tj, J, Ekv, D, lq, lg);
+            do {
+                const int p2 = paged_tile_page(lds_pg, tj + 2 * STEP, 0, J);
+                paged_load_tile(alt, kb, vb, pn, pg0, tj + STEP, J, Ekv, D,
+                                lq, lg);
+                gqa_tile_step_q<DC, NKC>(cur, qf, vt, tj, lim, lane, m, l,
+                                         oacc);
+                pn = paged_tile_page(lds_pg, tj + 3 * STEP, 0, J);
+                paged_load_tile(cur, kb, vb, p2, pg0, tj + 2 * STEP, J, Ekv,
+                                D, lq, lg);
+                gqa_tile_step_q<DC, NKC>(alt, qf, vt, tj + STEP, lim, lane, m,
+                                         l, oacc);
+                tj += 2 * STEP;
+            } while (tj < J);
+        }
+        // page ids are dead; after the last segment so are V tiles and Q
+        gqa_block_sync();
+        a = b;
+    }
+
+    // merge the 4 waves' partials in wave order (lane group 0 holds the
+    // column's (m, l); oacc[dc][jj] is O[d = dc*16 + lg*4 + jj][column lq])
+    if (lg == 0) {
+        lds_m[wid][lq] = m;
+        lds_l[wid][lq] = l;
+    }
+#pragma unroll
+    for (int dc = 0; dc < DC; ++dc) {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj)
+            lds_o[(wid * 16 + lq) * OSTR + dc * 16 + lg * 4 + jj] =
+                oacc[dc][jj];
+    }
+    gqa_block_sync();
+    const int col = tid >> 4;
+    if (col >= nq) return;
+    float mstar = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) mstar = fmaxf(mstar, lds_m[w][col]);
+    float wsc[NWAVES], lstar = 0.0f;
+#pragma unroll
+    for (int w = 0; w < NWAVES; ++w) {
+        const float mw = lds_m[w][col];         // -inf: no row of this wave
+        wsc[w] = (mw == -INFINITY) ? 0.0f : __expf(mw - mstar);
+        lstar += lds_l[w][col] * wsc[w];
+    }
+    for (int d = tid & 15; d < D; d += 16) {
+        float ostar = 0.0f;
+#pragma unroll
+        for (int w = 0; w < NWAVES; ++w)
+            ostar += lds_o[(w * 16 + col) * OSTR + d] * wsc[w];
+        gqa_store_out(ostar / lstar, h * D + d, t0 + col, E, jtw, out,
+                      out_prep);
+    }
+}
+
 // ============================================================== launchers
 
 void launch_paged_rows(hipStream_t s, const int* table, const int* pos,
@@ -294,4 +482,20 @@ void launch_attn_paged(hipStream_t s, const float* q_buf,
     if (S > 1)
         launch_attn_gqa_merge(s, ws, out, out_prep, pos, T, H, E, D, jtw,
                               chunk, S);
+}
+
+void launch_attn_paged_prefill(hipStream_t s, const float* q_buf,
+                               const __half* k_pool_layer,
+                               const __half* v_pool_layer, const int* table,
+                               float* out, unsigned short* out_prep,
+                               const int* pos, const int* seq, int T, int H,
+                               int Hkv, int E, int Ekv, int D, int n_ctx) {
+    const int npg = (n_ctx + PAGE_ROWS - 1) / PAGE_ROWS;
+    auto kern = D <= 16 ? k_attn_paged_prefill<1>
+              : D <= 32 ? k_attn_paged_prefill<2>
+              : D <= 64 ? k_attn_paged_prefill<4> : k_attn_paged_prefill<8>;
+    hipLaunchKernelGGL(kern, dim3((T + 15) / 16, H), dim3(BLOCK),
+                       sizeof(int) * (size_t)npg, s, q_buf, k_pool_layer,
+                       v_pool_layer, table, out, out_prep, pos, seq, T,
+                       H / Hkv, E, Ekv, D, npg, jt_width(T));
 }

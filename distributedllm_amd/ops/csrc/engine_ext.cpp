@@ -211,7 +211,7 @@ class SliceEngine {
                 int64_t n_head_kv = 0, bool gqa_attention = true,
                 int64_t kv_dtype = 0, bool kv8_prefill = true,
                 bool kv8_prefix = false, int64_t kv_layout = 0,
-                int64_t kv_pages = 0)
+                int64_t kv_pages = 0, bool paged_prefill = false)
         : E_((int)n_embd),
           H_((int)n_head),
           D_((int)(n_embd / n_head)),
@@ -225,11 +225,14 @@ class SliceEngine {
           kv8_prefill_(kv8_prefill),
           kv8_prefix_(kv8_prefix),
           paged_(kv_layout == 1),
+          paged_prefill_(paged_prefill),
           pages_(kv_pages) {
         TORCH_CHECK(kv_dtype == 0 || kv_dtype == 1,
                     "kv_dtype must be 0 (f16) or 1 (q8)");
         TORCH_CHECK(kv_layout == 0 || kv_layout == 1,
                     "kv_layout must be 0 (contiguous) or 1 (paged)");
+        TORCH_CHECK(paged_ || !paged_prefill_,
+                    "paged_prefill needs kv_layout paged");
         TORCH_CHECK(!paged_ || !kv8_,
                     "kv_layout paged holds an f16 cache: it cannot be "
                     "combined with kv_dtype q8");
@@ -421,7 +424,8 @@ class SliceEngine {
     // launch_attn_kv8_prefix over the byte caches. A paged engine runs
     // k_paged_rows once, then per layer qkv (with its finish pass, writing
     // straight into the pools through kv_row) and launch_attn_paged at every
-    // T; it refuses prefix. The caller keeps the block table covering every
+    // T (paged_prefill: launch_attn_paged_prefill for prompt spans > 64); it
+    // refuses prefix. The caller keeps the block table covering every
     // (seq[t], pos[t]) of the call.
     torch::Tensor forward(torch::Tensor x, torch::Tensor pos,
                           torch::Tensor seq, bool decode = false,
@@ -606,10 +610,17 @@ class SliceEngine {
                                     sp, T, H_, HK_, E_, EK_, D_, ctx_,
                                     kv8_ws_.data_ptr<float>());
             } else if (paged_) {
-                // every T, prompt spans included, per token over the pools
-                launch_attn_paged(s, qb, kc, vc, tbl, ab, aprep, pp, sp, T,
-                                  H_, HK_, E_, EK_, D_, ctx_,
-                                  paged_ws_.data_ptr<float>());
+                // per token over the pools at every T, prompt spans included,
+                // unless paged_prefill sends spans > 64 to the Q-tiled kernel
+                if (attn_paged_route(T, decode ? 1 : 0,
+                                     paged_prefill_ ? 1 : 0))
+                    launch_attn_paged_prefill(s, qb, kc, vc, tbl, ab, aprep,
+                                              pp, sp, T, H_, HK_, E_, EK_,
+                                              D_, ctx_);
+                else
+                    launch_attn_paged(s, qb, kc, vc, tbl, ab, aprep, pp, sp,
+                                      T, H_, HK_, E_, EK_, D_, ctx_,
+                                      paged_ws_.data_ptr<float>());
             } else if (shared) {
                 launch_attn_prefix(s, qb, kc, vc, ab, aprep, pp, sp, fp,
                                    pslot, plen, T, H_, HK_, E_, EK_, D_,
@@ -890,6 +901,7 @@ class SliceEngine {
     bool kv8_prefill_;       // q8 prompt spans > 64: k_attn_kv8_prefill
     bool kv8_prefix_;        // q8 serves prefix: launch_attn_kv8_prefix
     bool paged_;             // kv_layout paged: page pools, k_attn_paged
+    bool paged_prefill_;     // paged prompt spans > 64: k_attn_paged_prefill
     int64_t pages_;          // pages per layer pool (page 0 = scratch)
     std::vector<Layer> layers_;
     std::vector<bool> loaded_;
@@ -1224,12 +1236,14 @@ torch::Tensor paged_rows(torch::Tensor table, torch::Tensor pos,
 // k_attn_paged (+ k_attn_gqa_merge) over pools of f16 [pages * 16 * Ekv +
 // 16] (the pad is mandatory: the kernel reads whole 16-byte spans past the
 // last head); every table entry must name a page of the pools. The split-KV
-// workspace is per call.
-AttnResult attention_paged(torch::Tensor q, torch::Tensor k_pool,
-                           torch::Tensor v_pool, torch::Tensor table,
-                           torch::Tensor pos, torch::Tensor seq,
-                           int64_t n_head, int64_t n_head_kv,
-                           int64_t n_ctx) {
+// workspace is per call. prefill: k_attn_paged_prefill over the same
+// arguments (the engine runs it at T > 64).
+static AttnResult attention_paged_impl(torch::Tensor q, torch::Tensor k_pool,
+                                       torch::Tensor v_pool,
+                                       torch::Tensor table, torch::Tensor pos,
+                                       torch::Tensor seq, int64_t n_head,
+                                       int64_t n_head_kv, int64_t n_ctx,
+                                       bool prefill) {
     check_f32(q, "q");
     TORCH_CHECK(q.dim() == 2 && q.size(0) >= 1, "q must be [T, E]");
     TORCH_CHECK(n_head >= 1 && q.size(1) % n_head == 0,
@@ -1253,16 +1267,42 @@ AttnResult attention_paged(torch::Tensor q, torch::Tensor k_pool,
                     table.max().item<int64_t>() < pages,
                 "table entry out of [0, pages)");
     AttnResult r = alloc_attn_result(d);
+    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
+    if (prefill) {
+        launch_attn_paged_prefill(
+            s, q.data_ptr<float>(), h16c(k_pool), h16c(v_pool),
+            table.data_ptr<int>(), std::get<0>(r).data_ptr<float>(),
+            u16p(std::get<1>(r)), pos.data_ptr<int>(), seq.data_ptr<int>(),
+            d.T, d.H, d.Hkv, d.E, d.Ekv, d.D, d.ctx);
+        return r;
+    }
     auto ws = torch::zeros(
         {paged_ws_numel(d.H, d.D, d.ctx)},
         torch::TensorOptions().device(torch::kCUDA).dtype(torch::kFloat32));
-    hipStream_t s = c10::hip::getCurrentHIPStream().stream();
     launch_attn_paged(s, q.data_ptr<float>(), h16c(k_pool), h16c(v_pool),
                       table.data_ptr<int>(),
                       std::get<0>(r).data_ptr<float>(), u16p(std::get<1>(r)),
                       pos.data_ptr<int>(), seq.data_ptr<int>(), d.T, d.H,
                       d.Hkv, d.E, d.Ekv, d.D, d.ctx, ws.data_ptr<float>());
     return r;
+}
+
+AttnResult attention_paged(torch::Tensor q, torch::Tensor k_pool,
+                           torch::Tensor v_pool, torch::Tensor table,
+                           torch::Tensor pos, torch::Tensor seq,
+                           int64_t n_head, int64_t n_head_kv,
+                           int64_t n_ctx) {
+    return attention_paged_impl(q, k_pool, v_pool, table, pos, seq, n_head,
+                                n_head_kv, n_ctx, false);
+}
+
+AttnResult attention_paged_prefill(torch::Tensor q, torch::Tensor k_pool,
+                                   torch::Tensor v_pool, torch::Tensor table,
+                                   torch::Tensor pos, torch::Tensor seq,
+                                   int64_t n_head, int64_t n_head_kv,
+                                   int64_t n_ctx) {
+    return attention_paged_impl(q, k_pool, v_pool, table, pos, seq, n_head,
+                                n_head_kv, n_ctx, true);
 }
 
 // k_attn_prefix + k_attn_prefix_tail; the partials workspace is per call
@@ -1690,6 +1730,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("k_pool"), py::arg("v_pool"), py::arg("table"),
           py::arg("pos"), py::arg("seq"), py::arg("n_head"),
           py::arg("n_head_kv"), py::arg("n_ctx"));
+    m.def("attention_paged_prefill", &attention_paged_prefill, py::arg("q"),
+          py::arg("k_pool"), py::arg("v_pool"), py::arg("table"),
+          py::arg("pos"), py::arg("seq"), py::arg("n_head"),
+          py::arg("n_head_kv"), py::arg("n_ctx"));
+    m.def("attn_paged_route", [](int64_t T, bool decode, bool paged_prefill) {
+        return (int64_t)attn_paged_route((int)T, decode ? 1 : 0,
+                                         paged_prefill ? 1 : 0);
+    }, py::arg("T"), py::arg("decode"), py::arg("paged_prefill"));
     m.def("attn_paged_chunk", [](int64_t n_ctx) {
         return (int64_t)attn_paged_chunk((int)n_ctx);
     }, py::arg("n_ctx"));
@@ -1736,14 +1784,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     py::class_<SliceEngine, std::shared_ptr<SliceEngine>>(m, "SliceEngine")
         .def(py::init<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                       double, double, int64_t, int64_t, bool, int64_t,
-                      bool, bool, int64_t, int64_t>(),
+                      bool, bool, int64_t, int64_t, bool>(),
              py::arg("n_embd"), py::arg("n_head"), py::arg("n_layers"),
              py::arg("n_ff"), py::arg("n_ctx"), py::arg("max_batch"),
              py::arg("eps"), py::arg("rope_base"),
              py::arg("max_prefill") = 1024, py::arg("n_head_kv") = 0,
              py::arg("gqa_attention") = true, py::arg("kv_dtype") = 0,
              py::arg("kv8_prefill") = true, py::arg("kv8_prefix") = false,
-             py::arg("kv_layout") = 0, py::arg("kv_pages") = 0)
+             py::arg("kv_layout") = 0, py::arg("kv_pages") = 0,
+             py::arg("paged_prefill") = false)
         .def("set_layer", &SliceEngine::set_layer)
         .def("set_extra", &SliceEngine::set_extra)
         .def("forward", &SliceEngine::forward, py::arg("x"),

@@ -268,9 +268,21 @@ void launch_attn_kv8_prefix(hipStream_t s, const float* q_buf,
 //                      S = attn_paged_splits(n_ctx, 1); untouched when S = 1.
 //                      Dynamic LDS holds ceil(chunk / 16) page ids: callers
 //                      keep n_ctx <= 65536.
+//   launch_attn_paged_prefill  k_attn_paged_prefill: launch_attn_prefill's
+//                      semantics over the pools, any T >= 1, 1 <= H/Hkv <= 64,
+//                      D even and <= 128. One block per (16-query tile, query
+//                      head), the tile's queries as the MFMA columns, so a
+//                      K/V row is read once per 16 queries. No split-KV, no
+//                      workspace. A token's bits do not depend on its tile
+//                      mates, its column, T or which pages hold its rows.
+//                      Dynamic LDS holds one table row, ceil(n_ctx / 16)
+//                      page ids: callers keep n_ctx <= 65536.
+//   attn_paged_route   which of the two the engine runs: 1 (Q-tiled) iff
+//                      T > 64, not decode and paged_prefill, else 0.
 int kv_page_rows();
 int attn_paged_chunk(int n_ctx);
 int attn_paged_splits(int n_ctx, int T);
+int attn_paged_route(int T, int decode, int paged_prefill);
 
 void launch_paged_rows(hipStream_t s, const int* table, const int* pos,
                        const int* seq, int* kv_row, int T, int n_ctx);
@@ -281,6 +293,13 @@ void launch_attn_paged(hipStream_t s, const float* q_buf,
                        float* out, unsigned short* out_prep, const int* pos,
                        const int* seq, int T, int H, int Hkv, int E, int Ekv,
                        int D, int n_ctx, float* ws);
+
+void launch_attn_paged_prefill(hipStream_t s, const float* q_buf,
+                               const __half* k_pool_layer,
+                               const __half* v_pool_layer, const int* table,
+                               float* out, unsigned short* out_prep,
+                               const int* pos, const int* seq, int T, int H,
+                               int Hkv, int E, int Ekv, int D, int n_ctx);
 
 // ------------------------------------------------ shared-prefix attention
 // Token t attends rows [0, pfx[t]) of slot `pslot`, then rows

@@ -33,6 +33,11 @@ def main():
     ap.add_argument("--kv-dtype", default="f16", choices=["f16", "q8"])
     ap.add_argument("--no-kv8-prefill", action="store_true",
                     help="q8: keep the per-token k_attn_kv8 at T > 64")
+    ap.add_argument("--kv-layout", default="contiguous",
+                    choices=["contiguous", "paged"])
+    ap.add_argument("--paged-prefill", action="store_true",
+                    help="paged: the Q-tiled k_attn_paged_prefill at T > 64 "
+                         "instead of the per-token k_attn_paged")
     ap.add_argument("--layers", type=int, default=0,
                     help="build only the first N layers (0: the preset's)")
     args = ap.parse_args()
@@ -44,7 +49,11 @@ def main():
                                 n_ctx=ctx, max_batch=max(args.streams, 1),
                                 seed=0, with_extra=True, max_prefill=ctx,
                                 kv_dtype=args.kv_dtype,
-                                kv8_prefill=not args.no_kv8_prefill)
+                                kv8_prefill=not args.no_kv8_prefill,
+                                kv_layout=args.kv_layout,
+                                paged_prefill=args.paged_prefill)
+    for slot in range(max(args.streams, 1)):  # paged: pages for every span
+        assert eng.kv_reserve(slot, ctx)
     g = torch.Generator(device="cuda")
     g.manual_seed(1)
     for S in spans:
@@ -69,7 +78,9 @@ def main():
             "ms": round(dt * 1e3, 2), "ftype": args.ftype,
             "model": p.name, "layers": args.layers or p.n_layer,
             "kv_dtype": args.kv_dtype,
-            "kv8_prefill": not args.no_kv8_prefill}), flush=True)
+            "kv8_prefill": not args.no_kv8_prefill,
+            "kv_layout": args.kv_layout,
+            "paged_prefill": args.paged_prefill}), flush=True)
 
 
 if __name__ == "__main__":
